@@ -15,7 +15,8 @@ place, in index order: particle k sees every change made by particles < k in the
 generation -- computed on the device by its dependency DAG, bitwise the serial loop
 (csrc/srnn_ordered.h).  ``synchronous`` is the Jacobi variant (every read from the
 generation-start table): different dynamics, reported only as a side number
-(``config.jacobi``) next to the reference-order headline on one GPU.
+(``config.jacobi``) next to the reference-order headline on one GPU, and only with ``--full``:
+a plain run sets up, warms up, times ``--steps`` generations and prints the line.
 
 Scaling (``--scaling``): ``strong`` (default) is the metric as BASELINE.json writes it -- ONE
 100k-particle soup at any GPU count (100k / N particles per rank); ``weak`` keeps
@@ -29,7 +30,9 @@ ONE all-to-all per generation on the soup's own RCCL communicator over xGMI
 
 value = particles x generations / second over the whole job (max time over ranks).
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+       --full: also the side measurement (the other order); --dump-outputs: the soup after the
+       timed steps as DIR/<name>.npy, identical from run to run for the same arguments.
        N > 1 without torchrun's env: bench.py launches torch.distributed.run itself (one rank
        per GPU, RCCL over xGMI) as a child process and relays rank 0's JSON line.
 """
@@ -58,10 +61,18 @@ def parse_args(argv=None):
                     help="sequential (default): the reference's in-place, index-ordered generation (DAG-scheduled, "
                          "bitwise the serial loop; sharded by replicated plan + per-level all-gathers); synchronous: "
                          "the Jacobi variant, every read from the generation-start table")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, ALSO measure what rides along in the line: the same soup in the OTHER "
+                         "order (--side-steps).  Off by default: a plain run sets up, warms up, times --steps "
+                         "generations and prints the line")
     ap.add_argument("--side-steps", "--reference-order-steps", dest="side_steps", type=int, default=None,
-                    help="ALSO time this many generations of the same soup in the OTHER order on the same ranks "
-                         "(config.jacobi beside a reference-order headline, config.reference_order beside a Jacobi "
-                         "one); -1: --steps; default: --steps on one GPU, off on several; 0: off")
+                    help="with --full: time this many generations of the same soup in the OTHER order on the same "
+                         "ranks (config.jacobi beside a reference-order headline, config.reference_order beside a "
+                         "Jacobi one); -1: --steps; default: --steps on one GPU, off on several; 0: off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they left behind -- the soup a caller of evolve() holds "
+                         "-- as DIR/<name>.npy: weights (float32 [particles, P]), uids and that soup's census "
+                         "(float64); several ranks write <name>.rank<r>.npy, each its own shard")
     ap.add_argument("--train", type=int, default=20)
     ap.add_argument("--attacking-rate", type=float, default=0.1)
     ap.add_argument("--learn-from-rate", type=float, default=0.1)
@@ -76,7 +87,12 @@ def parse_args(argv=None):
                     help="rehearsal on a 1-GPU box: every rank uses cuda:0")
     ap.add_argument("--force-sharded", action="store_true",
                     help="rehearsal: run the multi-GPU generation (RCCL all-to-all) even with one rank")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.side_steps and not args.full:
+        ap.error("--side-steps times a second soup: it needs --full")
+    return args
 
 
 def _free_port() -> int:
@@ -164,6 +180,22 @@ def _side(args, order, spec, n_total, params, dev, d, execution, k_side, sync, b
         return {"semantics": label, "error": f"{type(e).__name__}: {e}"[:500]}
 
 
+def dump_outputs(path, eng, spec, census, d):
+    """--dump-outputs: the soup the timed generations left on this rank, as a caller of evolve()
+    reads it back -- weights, uids, and the census of that soup (global, in the class order of the
+    line's final_census).  The soup is seeded (--seed) and the engine deterministic, so the same
+    arguments give the same files."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    tag = f".rank{d.rank}" if d.world > 1 else ""
+    weights = eng.local_rows()[:, :spec.P].float().cpu().numpy()
+    np.save(os.path.join(path, f"weights{tag}.npy"), np.ascontiguousarray(weights, dtype=np.float32))
+    np.save(os.path.join(path, f"uids{tag}.npy"), eng.uid.cpu().numpy().astype(np.float64))
+    if isinstance(census, dict) and d.rank == 0:
+        np.save(os.path.join(path, "census.npy"), np.array(list(census.values()), dtype=np.float64))
+
+
 def main(argv=None):
     args = parse_args(argv)
     in_launcher = "WORLD_SIZE" in os.environ
@@ -237,6 +269,8 @@ def main(argv=None):
     # turns: a timing, not a soup; its census is not taken)
     census = eng.count() if not oerr else "invalid: one-rank timing model (SRNN_ORDSH_EMULATE)"
     value = n_total * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, spec, census, d)
     # what RCCL itself reports about the soup's communicator on every rank (ncclCommCount /
     # ncclCommUserRank): the line shows that the collective really spanned N ranks
     comm = None
@@ -247,14 +281,16 @@ def main(argv=None):
         allr = allr.view(d.world, 2).cpu().tolist()
         comm = {"library": d.native.library, "rccl_nranks": [r[0] for r in allr],
                 "rccl_user_ranks": [r[1] for r in allr]}
-    # the same soup in the other order, timed after the headline's region: a second number, never
-    # part of the headline value
+    # --full: the same soup in the other order, timed after the headline's region: a second number,
+    # never part of the headline value
     side = None
-    k_side = args.side_steps
+    k_side = args.side_steps if args.full else 0
     if k_side is None:
         k_side = -1 if d.world == 1 else 0
     k_side = args.steps if k_side < 0 else k_side
     other = "synchronous" if args.order == "sequential" else "sequential"
+    multi_generation_graph = eng._chunk is not None
+    two_graph_chunks = any(c[3] is not None for c in eng._chunks)
     if k_side > 0:
         eng.release_graphs()
         side = _side(args, other, spec, n_total, params, dev, d, execution, k_side, sync, backend)
@@ -280,8 +316,8 @@ def main(argv=None):
             "config": {"model": model_string(args),
                        "global_batch": n_total, "particles_per_gpu": n_total / d.world, "seq_len": None,
                        "parallelism": f"population-dp{d.world}", "device": args.device, "hip_graph": graphed,
-                       "multi_generation_graph": eng._chunk is not None,
-                       "two_graph_chunks": any(c[3] is not None for c in eng._chunks),
+                       "multi_generation_graph": multi_generation_graph, "two_graph_chunks": two_graph_chunks,
+                       "full": args.full,
                        "collectives": comm if comm is not None
                        else (f"torch.distributed ({backend})" if d.enabled else None),
                        "world_size": d.world, "execution": execution.in_force(),

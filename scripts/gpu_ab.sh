@@ -3,7 +3,8 @@
 # inside one call): a baseline directory holding bench.py + the package + its libsrnn.so (e.g.
 # `git worktree add ab_base <commit>` plus its built library) against this tree, alternated,
 # in the driver's form.  Extra arguments go to both bench runs; environment variables set on
-# the command line (SRNN_* knobs) apply to both.
+# the command line (SRNN_* knobs) apply to both.  The other order's number is printed when the
+# bench args hold --full (a baseline from before that option times it by default).
 #   bash scripts/gpu_ab.sh <tag> <baseline dir> [reps] [bench args...]
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"

@@ -17,8 +17,10 @@ done
 for i in $(seq 1 $REPS); do
   for V in base cand; do
     L=""; [ $V = cand ] && L=$PWD/$CAND
-    SRNN_LIB=$L timeout -k 10 300 python bench.py --steps 20 --warmup 5 > gpurun_out/b_${V}_${i}_$TAG.log 2>&1 || exit 1
-    python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().splitlines()[-1]); j=d['config'].get('jacobi') or {}; print(sys.argv[2], sys.argv[3], 'ref-order ms/gen %.4f' % d['ms_per_step'], 'jacobi %s' % (('%.4f' % j['ms_per_step']) if j else '-'))" gpurun_out/b_${V}_${i}_$TAG.log $V $i
+    # --full: the Jacobi side number rides along in the line
+    B=$(mktemp -t b_${V}_${i}_$TAG.XXXXXX)
+    SRNN_LIB=$L timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $B 2>&1 || { tail -5 $B; exit 1; }
+    python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().splitlines()[-1]); j=d['config'].get('jacobi') or {}; print(sys.argv[2], sys.argv[3], 'ref-order ms/gen %.4f' % d['ms_per_step'], 'jacobi %s' % (('%.4f' % j['ms_per_step']) if j else '-'))" $B $V $i
   done
 done
 echo done

@@ -9,7 +9,8 @@ from self_replicating_neural_networks_amd.analysis import plots as P
 from self_replicating_neural_networks_amd.analysis.__main__ import main as cli
 from self_replicating_neural_networks_amd.setups import experiments as E
 
-REF = "/root/reference/code/results"
+# the reference's recorded results (its code/results/*.dill), stored as data: tests/golden/README.md
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_results")
 
 
 def test_pca_projection_recovers_plane():
@@ -36,7 +37,6 @@ def test_all_plots_on_our_experiments(tmp_path):
     assert os.path.exists(os.path.join(r4["dir"], "trajectorys.html"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted")
 def test_plots_reference_artifacts(tmp_path):
     src = os.path.join(REF, "Soup", "soup.dill")
     dst = tmp_path / "soup.dill"

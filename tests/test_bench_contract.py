@@ -66,8 +66,9 @@ def test_bench_world_size_mismatch_exits_nonzero():
 def test_bench_headline_is_the_reference_order():
     """the headline `value` is the reference's own soup semantics (in place, index order); a 1-rank
     run (the driver's BENCH form) carries the Jacobi variant of the same soup beside it
-    (config.jacobi), and --order synchronous swaps the two"""
-    d = _bench("--particles", "1500")
+    (config.jacobi) when run with --full, and --order synchronous swaps the two; a plain run times
+    the headline only"""
+    d = _bench("--particles", "1500", "--full")
     assert d["semantics"] == "reference-order" and d["config"]["order"] == "sequential"
     assert "reference (sequential) order" in d["config"]["model"]
     lv = d["config"]["ordered_levels"]
@@ -76,17 +77,39 @@ def test_bench_headline_is_the_reference_order():
     j = d["config"]["jacobi"]
     assert j is not None and j["semantics"] == "jacobi" and j["steps"] == d["steps"]
     assert j["ms_per_step"] > 0 and j["value"] > 0 and sum(j["final_census"].values()) == 1500
-    off = _bench("--particles", "1500", "--side-steps", "0")
+    off = _bench("--particles", "1500", "--full", "--side-steps", "0")
     assert off["config"]["jacobi"] is None and off["config"]["reference_order"] is None
     # the same reference-order soup whatever else runs in the process
     assert off["config"]["final_census"] == d["config"]["final_census"]
-    sync = _bench("--particles", "1500", "--order", "synchronous")
+    plain = _bench("--particles", "1500")
+    assert plain["config"]["jacobi"] is None and plain["config"]["reference_order"] is None
+    assert plain["config"]["final_census"] == d["config"]["final_census"]
+    sync = _bench("--particles", "1500", "--order", "synchronous", "--full")
     assert sync["semantics"] == "jacobi" and sync["config"]["jacobi"] is None
     ro = sync["config"]["reference_order"]
     assert ro["semantics"] == "reference-order" and ro["final_census"] == d["config"]["final_census"]
     assert ro["levels"]["error"] == 0
     # the old spelling of the side-measurement flag still works
     assert _bench("--particles", "1500", "--reference-order-steps", "0")["config"]["jacobi"] is None
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the soup the timed steps left (weights float32, uids and census
+    float64) and the same arguments give the same files, bit for bit; --steps sets how many
+    generations ran"""
+    import numpy as np
+
+    a = _bench("--particles", "1500", "--dump-outputs", str(tmp_path / "a"))
+    _bench("--particles", "1500", "--dump-outputs", str(tmp_path / "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["census.npy", "uids.npy", "weights.npy"]
+    for name in ("weights", "uids", "census"):
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == (np.float32 if name == "weights" else np.float64)
+        assert x.tobytes() == y.tobytes(), name
+    w = np.load(tmp_path / "a" / "weights.npy")
+    assert w.shape == (1500, 14) and np.isfinite(w).all()
+    assert np.load(tmp_path / "a" / "census.npy").tolist() == list(a["config"]["final_census"].values())
+    assert a["steps"] == 2 and a["ms_per_step"] > 0
 
 
 def test_bench_reference_order_on_two_ranks():
@@ -98,6 +121,6 @@ def test_bench_reference_order_on_two_ranks():
     assert two["config"]["jacobi"] is None  # on request only
     one = _bench("--particles", "1200", "--side-steps", "0")
     assert two["config"]["final_census"] == one["config"]["final_census"]
-    side = _bench("--gpus", "2", "--particles", "1200", "--order", "synchronous", "--side-steps", "-1")
+    side = _bench("--gpus", "2", "--particles", "1200", "--order", "synchronous", "--full", "--side-steps", "-1")
     assert side["semantics"] == "jacobi"
     assert side["config"]["reference_order"]["final_census"] == one["config"]["final_census"]

@@ -12,11 +12,10 @@ from self_replicating_neural_networks_amd.experiment import Experiment, Fixpoint
 from self_replicating_neural_networks_amd.io import refpickle as R
 from self_replicating_neural_networks_amd.soup import Soup
 
-REF = "/root/reference/code/results"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted")
+# the reference's recorded results (its code/results/*.dill), stored as data: tests/golden/README.md
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_results")
 
 
-@needs_ref
 def test_reads_reference_soup_without_executing_code():
     s = R.load(os.path.join(REF, "Soup", "soup.dill"))
     assert isinstance(s, R.SoupRecord)
@@ -26,7 +25,6 @@ def test_reads_reference_soup_without_executing_code():
     assert isinstance(s.generator, R.Opaque)  # the pickled lambda stays inert
 
 
-@needs_ref
 def test_reads_learn_from_soup_uids():
     s = R.load(glob.glob(os.path.join(REF, "exp-learn-from-soup-*", "soup.dill"))[0])
     assert sorted(s.historical_particles) == list(range(1090, 1100))  # process-global uids (S13)
@@ -34,7 +32,6 @@ def test_reads_learn_from_soup_uids():
     assert acts.count("init") == 10 and acts.count("learn_from") == 98
 
 
-@needs_ref
 def test_reads_every_reference_artifact():
     files = glob.glob(os.path.join(REF, "**", "*.dill"), recursive=True)
     assert len(files) >= 20

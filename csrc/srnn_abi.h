@@ -73,6 +73,9 @@ enum SrnnFlag : uint32_t {
                                      // the counter only; the census of the final rows (block-stat class
                                      // counts) is OP_ORD_CENSUS's, issued on the side stream beside the
                                      // next generation
+  SRNN_F_TRAJ_STATE = 1u << 30,       // OP_RUN_FIXPOINT on the chunk-state kernels of the big aggregating nets:
+                                      // traj is the chunk-state trajectory float[steps][n][aggregates] (the
+                                      // state after step s at [s-1], zero-filled by the caller), not rows
 };
 
 // Attack-list entries (uint32, SRNN_NIL ends a list).  Single rank: the attacker's row
@@ -100,7 +103,9 @@ struct SrnnArgs {
                         // fraction x_emul / 2^32 of the local slots is marked remote-dependent
   float* W;             // rows [n][pp] (in/out)
   float* W2;            // second table (source rows / output rows)
-  float* traj;          // fixpoint run trajectory [(steps+1)][n][pp] or null
+  float* traj;          // fixpoint run trajectory [(steps+1)][n][pp] or null, zero-filled by the caller (the
+                        // chunk-state kernels of the big aggregating nets then need nsteps and temp >=
+                        // srnn_big_fix_temp_bytes(.., dense = 1)); SRNN_F_TRAJ_STATE: chunk states
   const int64_t* idx_f; // apply: applying-net row per item (null = identity)
   const int64_t* idx_t; // apply: target row per item (null = identity)
   const int64_t* idx_o; // apply: output row per item (null = identity)
@@ -297,4 +302,8 @@ int srnn_get_knob(int knob);
 // finished flag[1] is 1 when the two streams ran concurrently, 2 when the waiter timed out
 int srnn_stream_probe(int32_t* flag, void* side, void* main_stream, int64_t timeout_us);
 int64_t srnn_generic_scratch_bytes(const SrnnCfg* cfg, int64_t n, int64_t max_lanes);
+// temp bytes of a chunk-state run_fixpoint (big aggregating nets) over n rows: state float[n][aggregates] +
+// flags int8[n]; dense != 0: + (16-byte aligned) the chunk-state trajectory float[steps][n][aggregates]
+// that a dense recording is expanded from
+int64_t srnn_big_fix_temp_bytes(int aggregates, int64_t n, int steps, int dense);
 }

@@ -431,6 +431,28 @@ __global__ __launch_bounds__(TBB) void k_big(SrnnCfg c, SrnnArgs a) {
 //   chunk index of every weight a compile-time constant (fully unrolled MLP);
 // phase 3 (wave per particle): expand the final state into the row, coalesced.
 // temp = state float[n][A] followed by flags int8[n] (1 = continues in phase 2).
+//
+// Recording (a.traj): phases 1 and 2 also write the chunk-state trajectory float[steps][n][A],
+// the state after step s at [s - 1][p] for 1 <= s <= nsteps[p] (16 bytes per particle and step,
+// consecutive lanes -> consecutive particles; nothing for rows that stop at step 0).  With
+// SRNN_F_TRAJ_STATE that is the caller's (zero-filled) traj.  Without it traj is the dense
+// [(steps + 1)][n][PP] recording: the states go to temp behind the flags (big_straj_off) and
+// k_big_traj_expand writes row (s, p) <- expand(states[s - 1][p]) for s <= nsteps[p]; row 0 is
+// the input table, copied before phase 1.  The kernels of phases 1 and 2 get the state
+// trajectory in their a.traj either way (big_run hands them a copy of the arguments).
+
+// offset (bytes) in temp of the chunk-state trajectory of a dense recording
+constexpr int64_t big_straj_off(int A, int64_t n) { return (n * (A * 4 + 1) + 15) & ~(int64_t)15; }
+
+template <class T>
+__device__ __forceinline__ void store_chunk_state(float* dst, const float* s) {
+  if constexpr (T::A == 4) {
+    *reinterpret_cast<float4*>(dst) = make_float4(s[0], s[1], s[2], s[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < T::A; ++i) dst[i] = s[i];
+  }
+}
 
 template <class T, int L>
 __device__ __forceinline__ void dense_state_lane(const float* s, const float* x, float* y) {
@@ -493,6 +515,7 @@ __global__ __launch_bounds__(TBB) void k_big_fix1(SrnnCfg c, SrnnArgs a) {
 #pragma unroll
     for (int q = 1; q < T::A; ++q) v = (lane == q) ? h[q] : v;
     state[p * T::A + lane] = v;
+    if (a.traj) a.traj[p * T::A + lane] = v;  // recorded step 1
     if (lane == 0) flag[p] = 1;
   }
 }
@@ -508,12 +531,20 @@ __global__ __launch_bounds__(256) void k_big_fix2(SrnnCfg c, SrnnArgs a) {
 #pragma unroll
   for (int i = 0; i < T::A; ++i) st[i] = state[p * T::A + i];
   int taken = 1;
+  // the aggregates of expand(st) are st itself, but for one case: a mean's sum starts from +0,
+  // so the mean of a chunk of -0 (products that underflowed) is +0; the max aggregators keep
+  // the sign of the chunk's first element (x + -0 == x for every x)
+  const float zs = c.aggregator == 0 ? 0.0f : -0.0f;
   for (int k = 1; k < a.steps; ++k) {
     if (a.early_exit && !finite_all<T>(st)) break;
-    mlp_state_lane<T>(st, st, h);
+    float g[T::A];
+#pragma unroll
+    for (int i = 0; i < T::A; ++i) g[i] = st[i] + zs;
+    mlp_state_lane<T>(st, g, h);
     if (a.early_exit && finite_all<T>(h) && close_all<T>(h, st, a.eps)) break;
 #pragma unroll
     for (int i = 0; i < T::A; ++i) st[i] = h[i];
+    if (a.traj) store_chunk_state<T>(a.traj + ((int64_t)k * a.n + p) * T::A, st);  // recorded step k + 1
     ++taken;
   }
 #pragma unroll
@@ -1011,6 +1042,7 @@ __global__ __launch_bounds__(TBROW) void k_big_fix1_row(SrnnCfg c, SrnnArgs a) {
   } else {
 #pragma unroll
     for (int i = 0; i < T::A; ++i) state[p * T::A + i] = h[i];
+    if (a.traj) store_chunk_state<T>(a.traj + p * T::A, h);  // recorded step 1
     flag[p] = 1;
   }
 }
@@ -1548,6 +1580,26 @@ __global__ __launch_bounds__(TBROW) void k_big_fix3_row(SrnnCfg c, SrnnArgs a) {
 #pragma unroll
   for (int i = 0; i < T::A; ++i) st[i] = on ? state[p * T::A + i] : 0.f;
   R::store_state_staged(a.W, on ? (int32_t)p : -1, st, s_stg + (threadIdx.x >> 6) * R::G::WAVE_U4);
+}
+
+// dense recording, lane per row, grid (256-row block, step - 1): row (s, p) of a.traj <-
+// expand(states[s - 1][p]) for s <= nsteps[p], staged like phase 3; the rows of later steps stay
+// as the caller zero-filled them.  states: the chunk-state trajectory in temp (big_straj_off)
+template <class T>
+__global__ __launch_bounds__(TBROW) void k_big_traj_expand(SrnnCfg c, SrnnArgs a) {
+  using R = BRow<T, StF32>;
+  __shared__ uint4 s_stg[(TBROW / 64) * R::G::WAVE_U4];
+  const int64_t p = (int64_t)blockIdx.x * TBROW + threadIdx.x;
+  if (blockIdx.x * (int64_t)TBROW + (threadIdx.x & ~63) >= a.n) return;  // whole wave past n
+  const int64_t s = (int64_t)blockIdx.y + 1;
+  const float* states = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.temp) + big_straj_off(T::A, a.n));
+  const bool on = p < a.n && s <= (int64_t)a.nsteps[p];
+  if (__ballot(on) == 0ull) return;  // none of the wave's rows got this far
+  float st[T::A];
+#pragma unroll
+  for (int i = 0; i < T::A; ++i) st[i] = on ? states[((s - 1) * a.n + p) * T::A + i] : 0.f;
+  // (the step's table as the base: the staged row index stays a 32-bit row of one table)
+  R::store_state_staged(a.traj + s * a.n * T::PP, on ? (int32_t)p : -1, st, s_stg + (threadIdx.x >> 6) * R::G::WAVE_U4);
 }
 
 // init / perturb / respawn of big rows in any storage format (lane per particle)
@@ -2171,17 +2223,43 @@ int big_run(int op, const SrnnCfg& c, const SrnnArgs& a) {
       if (row_kernels) hipLaunchKernelGGL((k_big_row<T, OP_APPLY>), dim3(g64), dim3(TBROW), 0, st, c, a);
       else hipLaunchKernelGGL((k_big<T, OP_APPLY>), dim3(gw), dim3(TBB), 0, st, c, a);
       break;
-    case OP_RUN_FIXPOINT:
+    case OP_RUN_FIXPOINT: {
       if (!a.temp || a.temp_bytes < a.n * (T::A * 4 + 1)) {
         set_error("run_fixpoint on wave-per-particle nets needs temp >= n*(4*aggregates+1) bytes");
         return -5;
       }
-      if (row_kernels) hipLaunchKernelGGL((k_big_fix1_row<T>), dim3(g64), dim3(TBROW), 0, st, c, a);
-      else hipLaunchKernelGGL((k_big_fix1<T>), dim3(gw), dim3(TBB), 0, st, c, a);
-      hipLaunchKernelGGL((k_big_fix2<T>), dim3(gl), dim3(256), 0, st, c, a);
+      // recording: phases 1 and 2 write the chunk-state trajectory b.traj (the caller's with
+      // SRNN_F_TRAJ_STATE, else in temp behind the flags, expanded into the dense a.traj below)
+      const bool rec = a.traj != nullptr && a.steps > 0, dense = rec && !(a.flags & SRNN_F_TRAJ_STATE);
+      SrnnArgs b = a;
+      b.traj = rec ? a.traj : nullptr;
+      if (dense) {
+        if (!a.nsteps || a.steps > 65535 ||
+            a.temp_bytes < big_straj_off(T::A, a.n) + (int64_t)a.steps * a.n * T::A * 4 ||
+            (reinterpret_cast<uintptr_t>(a.temp) & 15)) {
+          set_error("recording run_fixpoint on wave-per-particle nets needs nsteps, steps <= 65535 and a 16-byte "
+                    "aligned temp >= srnn_big_fix_temp_bytes(aggregates, n, steps, 1)");
+          return -5;
+        }
+        b.traj = reinterpret_cast<float*>(reinterpret_cast<char*>(a.temp) + big_straj_off(T::A, a.n));
+      }
+      if (rec && (reinterpret_cast<uintptr_t>(b.traj) & 15)) {
+        set_error("recording run_fixpoint on wave-per-particle nets needs a 16-byte aligned trajectory");
+        return -5;
+      }
+      if (a.traj && !(a.flags & SRNN_F_TRAJ_STATE) &&  // dense row 0: the input table
+          hipMemcpyAsync(a.traj, a.W, (size_t)a.n * T::PP * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        set_error("recording run_fixpoint: copy of the input table failed");
+        return -3;
+      }
+      if (row_kernels) hipLaunchKernelGGL((k_big_fix1_row<T>), dim3(g64), dim3(TBROW), 0, st, c, b);
+      else hipLaunchKernelGGL((k_big_fix1<T>), dim3(gw), dim3(TBB), 0, st, c, b);
+      hipLaunchKernelGGL((k_big_fix2<T>), dim3(gl), dim3(256), 0, st, c, b);
       if (row_kernels) hipLaunchKernelGGL((k_big_fix3_row<T>), dim3(g64), dim3(TBROW), 0, st, c, a);
       else hipLaunchKernelGGL((k_big_fix3<T>), dim3(gw), dim3(TBB), 0, st, c, a);
+      if (dense) hipLaunchKernelGGL((k_big_traj_expand<T>), dim3(g64, (unsigned)a.steps), dim3(TBROW), 0, st, c, a);
       break;
+    }
     case OP_CLASSIFY:
       if (row_kernels) hipLaunchKernelGGL((k_big_row<T, OP_CLASSIFY>), dim3(g64), dim3(TBROW), 0, st, c, a);
       else hipLaunchKernelGGL((k_big<T, OP_CLASSIFY>), dim3(gw), dim3(TBB), 0, st, c, a);

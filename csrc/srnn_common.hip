@@ -155,6 +155,10 @@ static int route(int op, const SrnnCfg* c, const SrnnArgs* a) {
 static int dispatch(int op, const SrnnCfg* c, const SrnnArgs* a) {
   if (op < 0) return route(0, c, a) >= 0 ? 0 : 1;
   const int r = route(op, c, a);
+  if (op == OP_RUN_FIXPOINT && (a->flags & SRNN_F_TRAJ_STATE) && !(r == 0 && c->kind == 1 && c->p > 64)) {
+    srnn::set_error("SRNN_F_TRAJ_STATE: only the chunk-state kernels of the big aggregating nets record chunk states");
+    return -5;
+  }
   if (r == 0) return dispatch_special(op, c, a);
   if (r == 1) {
     const int g = srnn_dispatch_generic(op, c, a);

@@ -1370,6 +1370,7 @@ __global__ __launch_bounds__(64) void k_rnn_wave(GShape s, SrnnArgs a) {
     } else if constexpr (OP == OP_RUN_FIXPOINT) {
       rw_load(s, GItem::rowp(s, a.W, i), r.w);
       rw_sync();
+      if (a.traj) rw_store(s, GItem::rowp(s, a.traj, i), r.w);  // recording, as GItem::run_fixpoint
       int st = 0;
       for (; st < a.steps; ++st) {
         if (a.early_exit && rw_diverged(s, r.w)) break;
@@ -1379,6 +1380,7 @@ __global__ __launch_bounds__(64) void k_rnn_wave(GShape s, SrnnArgs a) {
         if (a.early_exit && !rw_diverged(s, r.aux) && rw_within(s, r.aux, r.w, a.eps)) break;
         for (int k = lane; k < s.P; k += 64) r.w[k] = r.aux[k];
         rw_sync();
+        if (a.traj) rw_store(s, GItem::rowp(s, a.traj, (int64_t)(st + 1) * a.n + i), r.w);
       }
       rw_store(s, GItem::rowp(s, a.W, i), r.w);
       if (a.nsteps && lane == 0) a.nsteps[i] = st;
@@ -1498,7 +1500,7 @@ __global__ __launch_bounds__(64) void k_rnn_wave_soup(GShape s, SrnnArgs a) {
 }
 
 // recurrent nets at least RW_MIN_WIDTH wide whose three P-vectors fit a workgroup's LDS run
-// apply / train / learn / run_fixpoint (no trajectory) wave per particle
+// apply / train / learn / run_fixpoint wave per particle
 // knob SRNN_KNOB_RNN_WAVE = 0: lane path for every width (A/B tests)
 extern "C" void srnn_set_rnn_wave(int on) { srnn_set_knob(SRNN_KNOB_RNN_WAVE, on ? 1 : 0); }
 // width / depth-specialised instantiations (RNN(8|16|32, 2), RNN(8|16, 3); RNN(32, 3) fully
@@ -1530,8 +1532,7 @@ static bool rw_serves(int op, const GShape& s, const SrnnArgs& a) {
   if (s.P != s.koff[s.D] + s.W + 1 || s.HS != s.D * s.W + 1) return false;
   if (op == OP_SOUP_EVOLVE)  // single-rank generations (sharded exchanges: the lane path)
     return knob(SRNN_KNOB_RNN_SOUP, 1) != 0 && !(a.flags & (SRNN_F_X2 | SRNN_F_FULL_TABLE)) && a.heads && a.nexts;
-  if (op == OP_RUN_FIXPOINT) return a.traj == nullptr;
-  return op == OP_APPLY || op == OP_TRAIN || op == OP_LEARN;
+  return op == OP_APPLY || op == OP_TRAIN || op == OP_LEARN || op == OP_RUN_FIXPOINT;
 }
 static int rw_launch(int op, const GShape& s, const SrnnArgs& a) {
   if (a.n <= 0) return 0;

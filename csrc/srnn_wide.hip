@@ -219,6 +219,9 @@ __global__ __launch_bounds__(WTB) void k_wide(SrnnCfg c, SrnnArgs a) {
     } else if constexpr (OP == OP_RUN_FIXPOINT) {
       lds_load<T>(L.f, a.W + p * T::PP, lane);
       __builtin_amdgcn_wave_barrier();
+      // recording: row 0 = the input, row s + 1 = the weights after each accepted step (the rows
+      // of steps never taken stay as the caller zero-filled them)
+      if (a.traj) lds_store<T>(a.traj + p * T::PP, L.f, lane);
       int s = 0;
       for (; s < a.steps; ++s) {
         if (a.early_exit && !lds_all_finite<T>(L.f, lane)) break;
@@ -229,6 +232,7 @@ __global__ __launch_bounds__(WTB) void k_wide(SrnnCfg c, SrnnArgs a) {
         if (a.early_exit && lds_all_finite<T>(L.o, lane) && lds_all_close<T>(L.o, L.f, a.eps, lane)) break;
         for (int k = lane; k < T::PP; k += 64) L.f[k] = L.o[k];
         __builtin_amdgcn_wave_barrier();
+        if (a.traj) lds_store<T>(a.traj + ((int64_t)(s + 1) * a.n + p) * T::PP, L.f, lane);
       }
       lds_store<T>(a.W + p * T::PP, L.f, lane);
       if (a.nsteps && lane == 0) a.nsteps[p] = s;

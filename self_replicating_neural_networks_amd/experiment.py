@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .io import refpickle
+from .ops.kernels import StateTrajectory
 from .oracle.core import CLASS_NAMES
 
 
@@ -120,6 +121,11 @@ class FixpointExperiment(Experiment):
         """``run_net`` for every particle of a ``Population`` in one device launch;
         counters accumulate like repeated ``run_net`` calls."""
         eps = eps or 1e-4
+        # unshuffled aggregating nets record their chunk states (16 bytes per particle and step on
+        # Aggregating(4, w, d) instead of a row): the dense trajectory is never materialised
+        spec = population.spec
+        if record and spec.kind == "aggregating" and spec.shuffler == "none":
+            record = "state"
         cls, nsteps, traj = population.run_fixpoint(step_limit, eps, early_exit=early_exit, record=record)
         c = np.bincount(cls.cpu().numpy().astype(np.int64), minlength=5)
         for i, name in enumerate(CLASS_NAMES):
@@ -129,17 +135,26 @@ class FixpointExperiment(Experiment):
             for row in population.W[idx, : population.spec.P].cpu().numpy():
                 self.interesting_fixpoints.append(population.spec.unflatten(row))
         if record:
-            self._record_trajectories(population, traj.cpu().numpy(), nsteps.cpu().numpy())
+            self._record_trajectories(population, traj, nsteps.cpu().numpy())
         return {n: int(c[i]) for i, n in enumerate(CLASS_NAMES)}
 
     def _record_trajectories(self, population, traj, nsteps):
+        """``traj``: the dense trajectory [(steps+1), N, PP] (tensor or numpy) or a ``StateTrajectory``."""
         cname = population.spec.class_name
         P = population.spec.P
+        if isinstance(traj, StateTrajectory):
+            # one device-to-host copy of the compact form; rows are expanded per particle on the host
+            traj = StateTrajectory(traj.spec, traj.row0.cpu(), traj.states.cpu(), traj.nsteps.cpu())
+            particle = traj.particle
+        else:
+            dense = traj.cpu().float().numpy() if torch.is_tensor(traj) else traj
+            particle = lambda r: dense[: int(nsteps[r]) + 1, r, :P]  # noqa: E731
         for r, uid in enumerate(population.uid.cpu().tolist()):
-            states = [{"class": cname, "weights": traj[0, r, :P].copy(), "time": 0, "action": "init",
+            rows = particle(r)
+            states = [{"class": cname, "weights": rows[0].copy(), "time": 0, "action": "init",
                        "counterpart": None}]
             for s in range(1, int(nsteps[r]) + 1):
-                w = traj[s, r, :P]
+                w = rows[s]
                 if np.all(np.isfinite(w)):
                     states.append({"class": cname, "weights": w.copy(), "time": s})
             self.historical_particles[uid] = states

@@ -95,6 +95,7 @@ FLAG_ORD_NEXT = 1 << 26  # OP_ORD_PLAN: plan generation gen + 1 (the one after t
 FLAG_ORD_SYNC = 1 << 27  # OP_ORD_PLAN / OP_SOUP_ORDERED: ordered by the o_sync counters (two graphs, two streams)
 FLAG_ORD_INPLAN = 1 << 28  # OP_SOUP_ORDERED: the run launch builds the next generation's plan (*_next buffers)
 FLAG_ORD_CENSUS_LATER = 1 << 29  # OP_SOUP_ORDERED: the census is OP_ORD_CENSUS's, beside the next generation
+FLAG_TRAJ_STATE = 1 << 30  # OP_RUN_FIXPOINT (big aggregating nets): traj is the chunk states [steps][n][A], not rows
 
 X2_HDR = 12           # int64 header words of an exchange block
 X2_REMOTE_WAVES = 4096
@@ -195,6 +196,8 @@ def lib():
         L.srnn_supports.restype = ctypes.c_int
         L.srnn_generic_scratch_bytes.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int64, ctypes.c_int64]
         L.srnn_generic_scratch_bytes.restype = ctypes.c_int64
+        L.srnn_big_fix_temp_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+        L.srnn_big_fix_temp_bytes.restype = ctypes.c_int64
         L.srnn_set_force_generic.argtypes = [ctypes.c_int]
         L.srnn_set_force_generic.restype = None
         L.srnn_set_rnn_wave.argtypes = [ctypes.c_int]
@@ -324,6 +327,12 @@ def set_ww_wave(on: bool) -> None:
 def generic_scratch_bytes(spec, n: int, dtype: int = DTYPE_FP32, max_lanes: int = 65536) -> int:
     """Device scratch the runtime-shape engine needs for ``n`` rows (per-lane vectors)."""
     return int(lib().srnn_generic_scratch_bytes(ctypes.byref(make_cfg(spec, dtype)), int(n), int(max_lanes)))
+
+
+def big_fix_temp_bytes(spec, n: int, steps: int = 0, dense: bool = False) -> int:
+    """``temp`` bytes of a run_fixpoint on the chunk-state kernels (csrc/srnn_bignet.h): the states and
+    flags of ``n`` rows, plus -- ``dense`` -- the chunk-state trajectory a dense recording is expanded from."""
+    return int(lib().srnn_big_fix_temp_bytes(int(spec.aggregates), int(n), int(steps), 1 if dense else 0))
 
 
 def run(op: int, spec, args: SrnnArgs, cfg: SrnnCfg = None, dtype: int = DTYPE_FP32) -> None:

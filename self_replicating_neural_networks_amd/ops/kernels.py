@@ -10,6 +10,7 @@ Shapes are checked on the host before anything is launched.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 from typing import Optional, Tuple
 
@@ -61,17 +62,73 @@ def _check_idx(idx: Optional[torch.Tensor], n_items: int, n_rows: int, dev, name
             raise IndexError(f"{name} out of range [0, {n_rows}): min {lo} max {hi}")
 
 
-def is_wave_per_particle(spec) -> bool:
+def is_wave_per_particle(spec, W: Optional[torch.Tensor] = None) -> bool:
     """Nets too large for the register kernels run wave-per-particle: aggregating nets
     (csrc/srnn_bignet.hip, chunk-state multi-step) and width >= 16 weightwise nets
     (csrc/srnn_wide.hip, MFMA) -- for the shapes those files instantiate; every other
-    shape runs on the runtime-shape engine (csrc/srnn_generic.hip)."""
+    shape runs on the runtime-shape engine (csrc/srnn_generic.hip).  ``W``: the table the
+    question is about (host tables and, for run_fixpoint, 16-bit or shuffled ones run on
+    the runtime-shape engine); default: a float32 device table."""
+    if W is not None and W.device.type != "cuda":
+        return False
+    dt = dtype_code(W.dtype) if W is not None else _lib.DTYPE_FP32
     return (((spec.kind == "aggregating" and spec.P > 64) or (spec.kind == "weightwise" and spec.width >= 16))
-            and not _lib.is_generic(spec, _lib.OP_RUN_FIXPOINT))
+            and not _lib.is_generic(spec, _lib.OP_RUN_FIXPOINT, dt))
 
 
-def needs_chunk_state_temp(spec) -> bool:
-    return spec.kind == "aggregating" and spec.P > 64 and not _lib.is_generic(spec, _lib.OP_RUN_FIXPOINT)
+def needs_chunk_state_temp(spec, W: Optional[torch.Tensor] = None) -> bool:
+    """True when run_fixpoint of this table runs on the chunk-state kernels of the big
+    aggregating nets (k_big_fix1/2/3), which need the caller's ``temp``."""
+    return spec.kind == "aggregating" and spec.P > 64 and is_wave_per_particle(spec, W)
+
+
+def _chunk_columns(spec, device) -> torch.Tensor:
+    """Chunk index of every weight (``ArchSpec.chunks``), int64[P]."""
+    idx = torch.empty(spec.P, dtype=torch.int64)
+    for c, (start, length) in enumerate(spec.chunks):
+        idx[start:start + length] = c
+    return idx.to(device)
+
+
+@dataclasses.dataclass
+class StateTrajectory:
+    """Compact self-application trajectory of an unshuffled aggregating net: after its first
+    self-application the row is constant over each aggregation chunk, so step ``s >= 1`` of
+    particle ``p`` is the ``A`` chunk values ``states[s - 1, p]`` (zero past ``nsteps[p]``)
+    and ``row0`` holds the input rows."""
+    spec: object
+    row0: torch.Tensor     # [N, PP], the table's dtype
+    states: torch.Tensor   # [steps, N, A] float32
+    nsteps: torch.Tensor   # [N] int32
+
+    @property
+    def steps(self) -> int:
+        return self.states.shape[0]
+
+    def _expand(self, st: torch.Tensor, first_step: int) -> torch.Tensor:
+        """[k, N, A] states of steps first_step .. first_step + k - 1 -> rows [k, N, PP]."""
+        k, n = st.shape[0], st.shape[1]
+        out = torch.zeros((k, n, self.spec.PP), dtype=self.row0.dtype, device=st.device)
+        out[:, :, :self.spec.P] = st[:, :, _chunk_columns(self.spec, st.device)].to(self.row0.dtype)
+        step = torch.arange(first_step, first_step + k, device=st.device)[:, None]
+        out[step > self.nsteps.to(st.device)[None, :].to(torch.int64)] = 0
+        return out
+
+    def rows(self, s: int) -> torch.Tensor:
+        """The rows [N, PP] after step ``s`` (0: the input); zero rows past ``nsteps``."""
+        if not 0 <= s <= self.steps:
+            raise IndexError(f"step {s} outside the recording [0, {self.steps}]")
+        return self.row0.clone() if s == 0 else self._expand(self.states[s - 1:s], s)[0]
+
+    def full(self) -> torch.Tensor:
+        """The dense trajectory [(steps+1), N, PP], what ``record=True`` returns."""
+        return torch.cat([self.row0[None], self._expand(self.states, 1)])
+
+    def particle(self, r: int):
+        """Particle ``r``'s recorded steps, numpy [nsteps[r]+1, P]."""
+        k = int(self.nsteps[r])
+        rows = self.states[:k, r][:, _chunk_columns(self.spec, self.states.device)].to(self.row0.dtype)
+        return torch.cat([self.row0[r:r + 1, :self.spec.P], rows]).float().cpu().numpy()
 
 
 def _base_args(W: torch.Tensor, seed: int = 0, ctr: int = 0, scratch: Optional[torch.Tensor] = None) -> SrnnArgs:
@@ -129,29 +186,49 @@ def apply(spec, W: torch.Tensor, out: torch.Tensor, idx_f=None, idx_t=None, idx_
 
 
 def run_fixpoint(spec, W: torch.Tensor, steps: int, eps: float, early_exit: bool = True, with_sec: bool = True,
-                 record: bool = False, uid=None, seed=0, ctr=0) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+                 record=False, uid=None, seed=0, ctr=0):
     """Per-row ``FixpointExperiment.run_net`` (code/experiment.py:70-91), in place.
 
-    Returns (class int8[N], steps int32[N], trajectory [(steps+1), N, PP] or None)."""
+    Returns (class int8[N], steps int32[N], trajectory).  ``record=True``: the dense trajectory
+    [(steps+1), N, PP] (row 0 the input, zero rows past a particle's last step), for every net and
+    table; ``record="state"``: a ``StateTrajectory`` (unshuffled aggregating nets only, ValueError
+    otherwise); ``record=False``: None."""
     dt = _check_table(spec, W)
-    n = W.shape[0]
+    if record is not False and record is not True and record != "state":
+        raise ValueError(f"record must be False, True or 'state', got {record!r}")
+    compact = record == "state"
+    if compact and not (spec.kind == "aggregating" and spec.shuffler == "none"):
+        raise ValueError(f"record='state' needs an unshuffled aggregating net (chunk-constant rows), got {spec}")
+    n, steps = W.shape[0], int(steps)
     cls = torch.empty(n, dtype=torch.int8, device=W.device)
     nsteps = torch.empty(n, dtype=torch.int32, device=W.device)
-    traj = torch.zeros((steps + 1, n, spec.PP), dtype=W.dtype, device=W.device) if record else None
     a = _base_args(W, seed, ctr)
-    a.n, a.steps, a.eps, a.early_exit = n, int(steps), float(eps), int(bool(early_exit))
+    a.n, a.steps, a.eps, a.early_exit = n, steps, float(eps), int(bool(early_exit))
     a.flags = _lib.FLAG_FIX_SEC if with_sec else 0
-    a.W, a.cls, a.nsteps, a.traj = _p(W), _p(cls), _p(nsteps), _p(traj)
+    a.W, a.cls, a.nsteps = _p(W), _p(cls), _p(nsteps)
     a.uid = _p(_uid(uid, n, W.device))
-    temp = None
-    if is_wave_per_particle(spec) and record:
-        raise NotImplementedError("trajectory recording is not supported for wave-per-particle nets")
-    if needs_chunk_state_temp(spec):
-        if record:
-            raise NotImplementedError("trajectory recording is not supported for wave-per-particle nets")
-        temp = torch.empty(n * (4 * spec.aggregates + 1), dtype=torch.uint8, device=W.device)
+    # the route of THIS table (device, storage format, shuffler): the chunk-state kernels serve
+    # float32 device tables of unshuffled big aggregating nets, the runtime-shape engine the rest
+    chunk_state = needs_chunk_state_temp(spec, W)
+    traj = states = row0 = temp = None
+    if compact and chunk_state:  # the kernels write the chunk states themselves
+        row0 = W.clone()
+        states = torch.zeros((max(steps, 0), n, spec.aggregates), dtype=torch.float32, device=W.device)
+        a.traj = _p(states)
+        a.flags |= _lib.FLAG_TRAJ_STATE
+    elif record:
+        traj = torch.zeros((max(steps, 0) + 1, n, spec.PP), dtype=W.dtype, device=W.device)
+        a.traj = _p(traj)
+    if chunk_state:
+        temp = torch.empty(_lib.big_fix_temp_bytes(spec, n, steps, dense=traj is not None), dtype=torch.uint8,
+                           device=W.device)
         a.temp, a.temp_bytes = _p(temp), temp.numel()
     _lib.run(_lib.OP_RUN_FIXPOINT, spec, a, dtype=dt)
+    if compact:
+        if states is None:  # recorded densely: one weight per chunk
+            starts = torch.tensor([c[0] for c in spec.chunks], dtype=torch.int64, device=W.device)
+            row0, states = traj[0].clone(), traj[1:, :, starts].float()
+        return cls, nsteps, StateTrajectory(spec, row0, states, nsteps)
     return cls, nsteps, traj
 
 

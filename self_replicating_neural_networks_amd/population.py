@@ -118,8 +118,10 @@ class Population:
         return K.learn_from(self.spec, self.W, teachers, idx_t, epochs, self.lr, shuffle, uid=self.uid,
                             seed=self.seed, ctr=self._next_ctr(epochs))
 
-    def run_fixpoint(self, steps: int = 100, eps: float = 1e-4, early_exit: bool = True, record: bool = False,
+    def run_fixpoint(self, steps: int = 100, eps: float = 1e-4, early_exit: bool = True, record=False,
                      with_sec: bool = True):
+        """``record``: False, True (dense trajectory) or "state" (``K.StateTrajectory``, unshuffled
+        aggregating nets); see ``K.run_fixpoint``."""
         return K.run_fixpoint(self.spec, self.W, steps, eps, early_exit, with_sec, record, uid=self.uid,
                               seed=self.seed, ctr=self._next_ctr(steps + 2))
 

@@ -2099,7 +2099,7 @@ int big_soup_ordered(const SrnnCfg& c, const SrnnArgs& a) {
               "planned ahead), respawn and two-phase block stats (temp)");
     return -5;
   }
-  if (!ord_inplan_ok(a) || !ord_sync_ok(a)) return -5;
+  if (!ord_inplan_ok(a) || !ord_sync_ok(a) || !ord_census_later_ok(a)) return -5;
   if (a.o_census_temp) {
     set_error("big ordered generation: no census in the run launch (o_census_temp)");
     return -5;

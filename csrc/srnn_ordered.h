@@ -1118,6 +1118,15 @@ inline bool ord_sync_ok(const SrnnArgs& a) {
   }
   return true;
 }
+// SRNN_F_ORD_CENSUS_LATER leaves the class counts of the block stats to a later launch: only a
+// batched finish (SRNN_F_GEN_COUNTS) may follow -- the serial finish runs straight after the close
+// and would reduce counts nobody has written
+inline bool ord_census_later_ok(const SrnnArgs& a) {
+  if (!(a.flags & SRNN_F_ORD_CENSUS_LATER) || (a.flags & SRNN_F_GEN_COUNTS)) return true;
+  set_error("SRNN_F_ORD_CENSUS_LATER needs the batched finish (SRNN_F_GEN_COUNTS): the serial finish after the "
+            "close would read class counts that are not written yet");
+  return false;
+}
 // the next generation's plan arguments of an in-run planning generation (host path)
 inline SrnnArgs ord_next_plan_args(const SrnnArgs& a) {
   SrnnArgs pa = a;
@@ -1264,7 +1273,7 @@ int soup_ordered(const SrnnCfg& c, const SrnnArgs& a) {
               "planned ahead), respawn and 1 <= o_levels <= 16");
     return -5;
   }
-  if (!ord_inplan_ok(a) || !ord_sync_ok(a)) return -5;
+  if (!ord_inplan_ok(a) || !ord_sync_ok(a) || !ord_census_later_ok(a)) return -5;
   if (!a.dev) {
     const int32_t gen = I::gen_of(a);
     if (!planned) ord_plan_host<O::RB>(a, false);

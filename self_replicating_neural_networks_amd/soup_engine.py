@@ -349,6 +349,8 @@ class SoupEngine:
         self.err = torch.zeros(1, **i32)              # exchange error bits (X2_ERRORS)
         self.stats = False          # census every generation
         self.stats_with_sec = True
+        self._census_log = None     # census_log: [batch][6] history rows of the batched finish
+        self._census_log_rows = 0   # ... rows the most recent finish launch wrote
         self.recorder = None        # full reference-schema state recorder (compat Soup)
         self.trajectory = None      # sampled TrajectoryRecorder (large soups)
         self.metrics = None         # MetricsWriter (JSONL per-generation metrics)
@@ -853,9 +855,12 @@ class SoupEngine:
                 if self._sync:  # (two counter-ordered graphs)
                     fa.flags |= _lib.FLAG_ORD_SYNC
                     fa.o_sync = _p(self._osync)
-                if self._ord_census_side and (fa.flags & _lib.FLAG_FUSED_CENSUS):
+                if (self._ord_census_side and self.finish_mode == "batch"
+                        and (fa.flags & _lib.FLAG_FUSED_CENSUS)):
                     # the census of the final rows after the close: on the side stream beside the
                     # next run, or (two-graph chunks) by extra workgroups of the next run launch
+                    # (batched finish only: a serial finish follows its close at once and would
+                    # reduce class counts nobody has written yet)
                     fa.flags |= _lib.FLAG_ORD_CENSUS_LATER
                 if self._ord_mode == "kernel":  # the run launch also builds the next generation's plan
                     nsrc, nlist, nctl = self._ord_set(1 - q)
@@ -1139,6 +1144,9 @@ class SoupEngine:
         a.flags = (self._fin_flags & (_lib.FLAG_FUSED_CENSUS | _lib.FLAG_BORN_TOTAL)) | _lib.FLAG_FINISH_BATCH
         a.temp, a.temp_bytes = _p(self._bs_ring), self._bs_ring.stride(0) * 4
         a.uid_out, a.uid_base, a.counts = _p(self.uid), _p(self.next_uid), _p(self.counts)
+        if self._census_log is not None:  # (census_log: one history row per finished generation)
+            a.census = _p(self._census_log)
+            self._census_log_rows = m
         if self.execution.finish_par:
             a.done = _p(self._done)  # done counter: one finish workgroup per generation
         _lib.run(_lib.OP_GEN_FINISH, self.spec, a, self.cfg)
@@ -1431,6 +1439,39 @@ class SoupEngine:
         c = self.census if self.dist.enabled else self.counts[:5]
         return counts_dict(c.cpu())
 
+    @property
+    def census_log(self) -> bool:
+        """Opt-in (single rank, batched finish; set it with ``stats`` before ``capture()``): every
+        finish launch also writes one ``[classes[5], respawns]`` row per generation it finishes
+        (``census_history()``) -- ``counts`` keeps the launch's last generation only, so the
+        censuses taken inside a multi-generation chunk are visible nowhere else."""
+        return self._census_log is not None
+
+    @census_log.setter
+    def census_log(self, on: bool):
+        if bool(on) == (self._census_log is not None):
+            return
+        if self._graphs is not None or self._chunks:
+            raise ValueError("census_log must be set before capture(): the graphs hold the finish's arguments "
+                             "(release_graphs() first)")
+        if not on:
+            self._census_log, self._census_log_rows = None, 0
+            return
+        if self.dist.enabled or getattr(self, "finish_mode", None) != "batch":
+            raise ValueError("census_log needs a single-rank engine with finish_mode='batch' (a GPU soup of an "
+                             "instantiated shape)")
+        if self._census_log is None:
+            self._census_log = torch.zeros((self._batch, 6), dtype=torch.int64, device=self.device)
+            self._census_log_rows = 0
+
+    def census_history(self) -> torch.Tensor:
+        """``census_log``: rows ``[divergent, fix_zero, fix_other, fix_sec, other, respawns]`` of the
+        generations the most recent finish launch finished, oldest first (a G-generation chunk or
+        an eager ``evolve(G)`` with G <= the largest graph chunk: its G generations)."""
+        if self._census_log is None:
+            raise RuntimeError("census_log is off")
+        return self._census_log[: self._census_log_rows].cpu()
+
     def evolve(self, iterations: int = 1, record: bool = False):
         left = int(iterations)
         while left > 0:
@@ -1441,6 +1482,8 @@ class SoupEngine:
                 # G generations in one graph launch (no inter-graph gaps)
                 self._join_side()
                 self._replay_chunk(ch)
+                # (the chunk's finish launches, as captured: one per _batch generations and one at its end)
+                self._census_log_rows = (ch[2] - 1) % self._batch + 1 if self._census_log is not None else 0
                 self.time += ch[2]
                 left -= ch[2]
                 self._pending = self.dist.enabled
@@ -1456,6 +1499,7 @@ class SoupEngine:
             elif self._graphs is not None:
                 self._join_side()
                 self._graphs[self._p].replay()
+                self._census_log_rows = 1 if self._census_log is not None else 0
                 self._p = 1 - self._p
                 self._pending = self.dist.enabled
             else:
@@ -1513,7 +1557,7 @@ class SoupEngine:
                  "_done", "_bs_ring", "x_dep", "x_rlist", "x_rcount", "x_rslot", "x_satt", "x_cno", "x_crq",
                  "x_srep", "x_nsrep", "x_part", "x_ctl", "x_bstat", "x_hpre", "x_hgrp", "sendbuf", "recvbuf",
                  "_abuf", "_osrc", "_olist", "_octl", "_ptab", "_osrc1", "_olist1", "_octl1", "_ptab1", "_osync",
-                 "_fw", "_sh_heads", "_sh_nexts", "_sh_cnt", "_sh_send", "_sh_recv"]
+                 "_fw", "_sh_heads", "_sh_nexts", "_sh_cnt", "_sh_send", "_sh_recv", "_census_log"]
         out = []
         for k in names:
             v = getattr(self, k, None)
@@ -1785,6 +1829,10 @@ class SoupEngine:
         keep = {id(t) for t in self._bufs} | {id(getattr(self, k)) for k in (
             "uid", "next_uid", "_gen_ring", "counts", "census", "loss", "respawn", "action", "counterpart", "err")
             if isinstance(getattr(self, k, None), torch.Tensor)}
+        if parity_after is not None and self._census_log is not None:
+            # (a chunk finishes its generations in the launches the eager generations use, so the census
+            # log rows agree; two single-generation graphs finish one by one, the eager pair at once)
+            keep.add(id(self._census_log))
         if ring and isinstance(getattr(self, "_bs_ring", None), torch.Tensor):
             # (a chunk batches its finishes like the eager generations: every generation's census and
             # ballots, wherever they ran, compared too)

@@ -33,7 +33,7 @@ def test_device_ordered_big_net_is_the_host_serial_loop(dtype, shuffler):
     o = SoupEngine(spec, n, HOT, device="cuda", seed=seed, order="sequential", dtype=dtype)
     o.stats = True
     s = SequentialSoupEngine(spec, n, HOT, seed=seed, dtype=dtype, weights=o.local_rows()[:, :spec.P].float().cpu())
-    deep = 0
+    deep, uid0 = 0, n
     for g in range(3):
         o.evolve(1)
         s.evolve(1)
@@ -47,6 +47,12 @@ def test_device_ordered_big_net_is_the_host_serial_loop(dtype, shuffler):
         lv = o.ordered_levels()
         assert lv["error"] == 0
         deep = max(deep, lv["max_level"])
+        # the generation's census (fused into the big close; shuffle_random: classify_local after it) ==
+        # the classify kernel on its final rows; the ballots' count == the respawn flags == the uids drawn
+        census = o.last_census()
+        assert census == o.count() and sum(census.values()) == n, g
+        assert int(o.counts[5]) == int((o.respawn != 0).sum()) == int(o.next_uid[0]) - uid0, g
+        uid0 = int(o.next_uid[0])
     assert deep >= 2  # real dependency chains (recomputed and stored attack outputs)
     assert int(o.next_uid[0]) == int(s.next_uid[0])
     assert sum(o.count().values()) == n
@@ -56,12 +62,17 @@ def test_device_ordered_big_net_graphs_equal_eager():
     spec = ArchSpec.aggregating(4, 10, 3)
     a = SoupEngine(spec, 1500, HOT, device="cuda", seed=3, order="sequential")
     b = SoupEngine(spec, 1500, HOT, device="cuda", seed=3, order="sequential")
+    a.stats = b.stats = True
     assert b.capture(warmup=1)
     a.evolve(1)
     a.evolve(3)
     b.evolve(3)
     torch.cuda.synchronize()
     assert torch.equal(_bits(a.local_rows()), _bits(b.local_rows())) and torch.equal(a.uid, b.uid)
+    # the census of the last generation: eager == graphed == the classify kernel on the final rows
+    assert a.last_census() == a.count() == b.last_census() == b.count()
+    assert sum(b.last_census().values()) == 1500
+    assert int(a.counts[5]) == int(b.counts[5]) == int((b.respawn != 0).sum())
 
 
 @pytest.mark.parametrize("shape", [(4, 8, 2), (4, 16, 2)], ids=["agg-4-8-2", "agg-4-16-2"])

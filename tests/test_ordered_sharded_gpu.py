@@ -44,10 +44,12 @@ def _worker(rank, world, port, out_dir, dtype, chunks, n_total=N_TOTAL):
         for k in chunks:
             e.evolve(k)
         counts = e.count()
+        census = e.last_census()  # (the last generation's own census, all ranks' rows)
         torch.cuda.synchronize()
         np.savez(os.path.join(out_dir, f"r{rank}.npz"), W=e.local_rows().float().cpu().numpy(),
                  uid=e.uid.cpu().numpy(), next_uid=e.next_uid.cpu().numpy(), loss=e.loss.cpu().numpy(),
-                 counts=np.array([counts[k] for k in sorted(counts)]), err=np.array([e.ordered_error()]))
+                 counts=np.array([counts[k] for k in sorted(counts)]),
+                 census=np.array([census[k] for k in sorted(census)]), err=np.array([e.ordered_error()]))
     finally:
         dist.destroy_process_group()
 
@@ -71,3 +73,6 @@ def test_device_sharded_reference_order_equals_single_rank(tmp_path, world, dtyp
     for p in parts:
         assert int(p["next_uid"][0]) == int(ref.next_uid[0]) and int(p["err"][0]) == 0
         assert list(p["counts"]) == [ref_counts[k] for k in sorted(ref_counts)]
+        # the generation's own census (stats = True) == the classify kernel on the single-rank soup's rows
+        assert list(p["census"]) == [ref_counts[k] for k in sorted(ref_counts)]
+        assert int(p["census"].sum()) == n_total

@@ -1,0 +1,153 @@
+"""Reference-order soups of runtime shapes on the device: ms per generation.
+
+For WW(3,3), WW(10,3), Agg(4,4,3) and RNN(8,2) at the bench parameters (attack 0.1, learn 0.1,
+train 20, respawn) this times one generation of ``SoupEngine(order="sequential")`` -- the
+continuation-scheduled generation with the runtime-shape turn (csrc/srnn_generic.hip GOrd) --
+eagerly and replayed from hipGraphs, and reports its dependency levels.  Beside it: the
+synchronous (Jacobi) soup of the same shape with the wave kernels on and off, and the host serial
+loop (``SequentialSoupEngine``) at 2,000 particles scaled per particle.
+
+The driver runs every step in a child process of its own under a time limit and stops at the
+first step that fails; each step prints one JSON line.  ``--markdown`` adds the table of
+profiles/ordered_runtime_shapes.md.
+
+    python bench/ordered_shapes.py [--n 100000] [--gens 3] [--shapes ww33,ww103,agg443,rnn82]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PARAMS = dict(attacking_rate=0.1, learn_from_rate=0.1, train=20, learn_from_severity=1, remove_divergent=True,
+              remove_zero=True, epsilon=1e-4)
+SHAPES = {"ww33": ("weightwise", (3, 3)), "ww103": ("weightwise", (10, 3)), "agg443": ("aggregating", (4, 4, 3)),
+          "rnn82": ("recurrent", (8, 2))}
+STEPS = ("ordered-eager", "ordered-graph", "sync-waves", "sync-lanes", "host-serial")
+
+
+def _spec(shape):
+    from self_replicating_neural_networks_amd.arch import ArchSpec
+    kind, dims = SHAPES[shape]
+    return getattr(ArchSpec, kind)(*dims)
+
+
+def _timed(engine, gens):
+    import torch
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    engine.evolve(gens)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / gens * 1e3
+
+
+def step(name, shape, n, gens, host_n):
+    import torch
+    from self_replicating_neural_networks_amd.config import ExecConfig
+    from self_replicating_neural_networks_amd.seq_soup import SequentialSoupEngine
+    from self_replicating_neural_networks_amd.soup_engine import SoupEngine
+
+    spec = _spec(shape)
+    out = dict(shape=shape, step=name, P=spec.P)
+    if name == "host-serial":
+        e = SequentialSoupEngine(spec, host_n, PARAMS, seed=1)
+        e.evolve(1)
+        t = time.perf_counter()
+        e.evolve(1)
+        ms = (time.perf_counter() - t) * 1e3
+        out.update(n=host_n, ms_per_gen=round(ms, 3), us_per_particle=round(ms * 1e3 / host_n, 3),
+                   ms_scaled=round(ms * n / host_n, 1), scaled_to=n)
+        return out
+    if not torch.cuda.is_available():
+        raise SystemExit("ordered_shapes: no GPU (a measurement does not fall back to the host)")
+    if name.startswith("ordered"):
+        ex = ExecConfig(graph_chunks=(2,))
+        e = SoupEngine(spec, n, PARAMS, device="cuda", seed=1, order="sequential", execution=ex)
+        assert e._ord_generic, "not a runtime shape"
+        if name == "ordered-graph":
+            assert e.capture(warmup=1), "graph capture failed"
+        e.evolve(2)
+        ms = _timed(e, gens)
+        lv = e.ordered_levels()
+        assert lv["error"] == 0, lv
+        out.update(n=n, ms_per_gen=round(ms, 3), levels=lv["levels"], tail=lv["tail"], max_level=lv["max_level"],
+                   pending=lv["pending"], stored_attacks=lv["stored_attacks"],
+                   scratch_mb=round(e._scratch.numel() / 2 ** 20, 1), census=e.count())
+        e.release_graphs()
+        return out
+    waves = name == "sync-waves"
+    ex = ExecConfig(ww_wave=int(waves), rnn_wave=waves, rnn_soup=waves)
+    ex.apply_library()
+    e = SoupEngine(spec, n, PARAMS, device="cuda", seed=1, execution=ex)
+    e.evolve(2)
+    ms = _timed(e, gens)
+    out.update(n=n, ms_per_gen=round(ms, 3), census=e.count())
+    return out
+
+
+def markdown(rows, n):
+    by = {}
+    for r in rows:
+        by.setdefault(r["shape"], {})[r["step"]] = r
+    lines = [f"| shape | P | ordered eager ms | ordered graph ms | levels (+tail) | sync waves ms | sync lanes ms | "
+             f"host loop ms (scaled to {n}) | device vs host |", "|---|---|---|---|---|---|---|---|---|"]
+    for shape, d in by.items():
+        g = lambda k, f="ms_per_gen": d.get(k, {}).get(f, "not measured")  # noqa: E731
+        o = d.get("ordered-graph") or d.get("ordered-eager") or {}
+        lv = f"{o.get('levels')} + {o.get('tail')}" if o else "not measured"
+        h = d.get("host-serial", {}).get("ms_scaled")
+        best = min([x["ms_per_gen"] for k, x in d.items() if k.startswith("ordered")] or [0])
+        ratio = f"{h / best:.1f}x" if h and best else "not measured"
+        lines.append(f"| {shape} | {o.get('P', '')} | {g('ordered-eager')} | {g('ordered-graph')} | {lv} | "
+                     f"{g('sync-waves')} | {g('sync-lanes')} | {h if h else 'not measured'} | {ratio} |")
+    return "\n".join(lines)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=100000)
+    ap.add_argument("--gens", type=int, default=3)
+    ap.add_argument("--host-n", type=int, default=2000)
+    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--steps", default=",".join(STEPS))
+    ap.add_argument("--step-timeout", type=int, default=150)
+    ap.add_argument("--markdown", action="store_true")
+    ap.add_argument("--child", nargs=2, metavar=("STEP", "SHAPE"))
+    args = ap.parse_args()
+    if args.child:
+        print(json.dumps(step(args.child[0], args.child[1], args.n, args.gens, args.host_n)), flush=True)
+        return 0
+    rows = []
+    for shape in args.shapes.split(","):
+        for name in args.steps.split(","):
+            cmd = [sys.executable, os.path.abspath(__file__), "--n", str(args.n), "--gens", str(args.gens), "--host-n",
+                   str(args.host_n), "--child", name, shape]
+            try:
+                p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout, cwd=ROOT)
+            except subprocess.TimeoutExpired:
+                print(json.dumps(dict(shape=shape, step=name, error=f"time limit of {args.step_timeout} s")), flush=True)
+                if args.markdown:
+                    print(markdown(rows, args.n), flush=True)
+                return 124
+            if p.returncode != 0:
+                err = p.stderr if len(p.stderr) <= 1600 else p.stderr[:800] + " ... " + p.stderr[-800:]
+                print(json.dumps(dict(shape=shape, step=name, error=err, rc=p.returncode)), flush=True)
+                if args.markdown:
+                    print(markdown(rows, args.n), flush=True)
+                return p.returncode or 1
+            line = p.stdout.strip().splitlines()[-1]
+            print(line, flush=True)
+            rows.append(json.loads(line))
+    if args.markdown:
+        print(markdown(rows, args.n), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

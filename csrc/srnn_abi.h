@@ -302,6 +302,12 @@ int srnn_get_knob(int knob);
 // finished flag[1] is 1 when the two streams ran concurrently, 2 when the waiter timed out
 int srnn_stream_probe(int32_t* flag, void* side, void* main_stream, int64_t timeout_us);
 int64_t srnn_generic_scratch_bytes(const SrnnCfg* cfg, int64_t n, int64_t max_lanes);
+// reference-order generation of a runtime shape (srnn_generic.hip): lanes of the run launch of n turns,
+// the device scratch bytes OP_SOUP_ORDERED needs for them, and whether the runtime-shape engine serves
+// `op` of this configuration on the host (dev 0) / device (dev 1)
+int64_t srnn_ord_run_lanes(int64_t n);
+int64_t srnn_generic_ord_scratch_bytes(const SrnnCfg* cfg, int64_t n);
+int srnn_generic_supports(const SrnnCfg* cfg, int op, int dev);
 // temp bytes of a chunk-state run_fixpoint (big aggregating nets) over n rows: state float[n][aggregates] +
 // flags int8[n]; dense != 0: + (16-byte aligned) the chunk-state trajectory float[steps][n][aggregates]
 // that a dense recording is expanded from

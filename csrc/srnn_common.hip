@@ -179,7 +179,10 @@ static int64_t g_scratch_bytes[64] = {0};
 static int with_scratch(int op, const SrnnCfg* c, const SrnnArgs* a) {
   if (!a->dev || a->scratch || route(op, c, a) != 1 || op == OP_SOUP_DECIDE)
     return dispatch(op, c, a);
-  const int64_t want = srnn_generic_scratch_bytes(c, a->n, 65536);
+  // (a reference-order generation: one lane per turn of its run launch; a plan needs none)
+  if (op == OP_ORD_PLAN || op == OP_GEN_FINISH) return dispatch(op, c, a);
+  const int64_t want = op == OP_SOUP_ORDERED ? srnn_generic_ord_scratch_bytes(c, a->n)
+                                             : srnn_generic_scratch_bytes(c, a->n, 65536);
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64) dev = 0;
@@ -275,7 +278,7 @@ int srnn_supports(const SrnnCfg* cfg, int op, int dev) {
   probe.dev = dev;
   const int r = route(op, cfg, &probe);
   if (r == 0) return 1;
-  return r == 1 && srnn_generic_op_supported(op, dev) ? 1 : 0;
+  return r == 1 && srnn_generic_supports(cfg, op, dev) ? 1 : 0;
 }
 
 int srnn_run(int op, const SrnnCfg* cfg, const SrnnArgs* a) {

@@ -278,6 +278,41 @@ template <int NL>
 struct ShapeTable { Shape s[NL]; };
 
 // normalize_id (reference code/network.py:216-220): v/m if m > 1 else v
+// cos(x), 0 <= x < 8, the same bits on the host and on the device (the FFT nets' cosine factors).
+// libm's cosf is glibc's on the host and the device library's on the GPU; they differ in the last
+// bit for some of the 2 pi j / N the FFT nets use, which made an FFT attack differ between host and
+// device.  Here: double arithmetic with explicit fma only (IEEE on both sides), reduction by the
+// nearest multiple of pi/2 with a two-word pi/2, Taylor series on |r| <= pi/4 to r^16 / r^17 (error
+// < 1e-17), rounded to float once -- the correctly rounded cosine but for results within ~1e-16 of
+// a float rounding boundary.
+SRNN_HD float cos_hd(float xf) {
+  const double x = (double)xf;
+  const int q = (int)fma(x, 0.63661977236758134308, 0.5);  // nearest multiple of pi/2
+  double r = fma(-(double)q, 1.57079632679489655800e+00, x);
+  r = fma(-(double)q, 6.12323399573676603587e-17, r);
+  const double z = r * r;
+  double c = 1.0 / 20922789888000.0;  // 1/16!
+  c = fma(c, z, -1.0 / 87178291200.0);
+  c = fma(c, z, 1.0 / 479001600.0);
+  c = fma(c, z, -1.0 / 3628800.0);
+  c = fma(c, z, 1.0 / 40320.0);
+  c = fma(c, z, -1.0 / 720.0);
+  c = fma(c, z, 1.0 / 24.0);
+  c = fma(c, z, -0.5);
+  c = fma(c, z, 1.0);
+  double s = 1.0 / 355687428096000.0;  // 1/17!
+  s = fma(s, z, -1.0 / 1307674368000.0);
+  s = fma(s, z, 1.0 / 6227020800.0);
+  s = fma(s, z, -1.0 / 39916800.0);
+  s = fma(s, z, 1.0 / 362880.0);
+  s = fma(s, z, -1.0 / 5040.0);
+  s = fma(s, z, 1.0 / 120.0);
+  s = fma(s, z, -1.0 / 6.0);
+  s = fma(s * z, r, r);
+  const int m = q & 3;
+  return (float)(m == 0 ? c : m == 1 ? -s : m == 2 ? -c : s);
+}
+
 constexpr float norm_id(int v, int m) { return m > 1 ? (float)v / (float)m : (float)v; }
 
 template <int P>
@@ -865,7 +900,7 @@ struct FFTNet {
     for (int k = 0; k < A; ++k) {
       float acc = 0.f;
 #pragma unroll
-      for (int n = 0; n < A; ++n) acc = fmaf(t[n], cosf(6.283185307179586f * (float)((k * n) % A) / (float)A), acc);
+      for (int n = 0; n < A; ++n) acc = fmaf(t[n], cos_hd(6.283185307179586f * (float)((k * n) % A) / (float)A), acc);
       g[k] = acc;
     }
   }
@@ -878,7 +913,7 @@ struct FFTNet {
     for (int m = 0; m < P; ++m) {
       float acc = 0.f;
 #pragma unroll
-      for (int k = 0; k < A; ++k) acc = fmaf(h[k], cosf(6.283185307179586f * (float)((k * m) % P) / (float)P), acc);
+      for (int k = 0; k < A; ++k) acc = fmaf(h[k], cos_hd(6.283185307179586f * (float)((k * m) % P) / (float)P), acc);
       out[m] = acc / (float)P;
     }
     shuffle_out<P>(out, c);

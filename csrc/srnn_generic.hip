@@ -357,7 +357,7 @@ SRNN_HD void g_fft_reduce(const GShape& s, const SV& t, SV g) {
   for (int k = 0; k < s.A; ++k) {
     float acc = 0.f;
     for (int n = 0; n < s.A; ++n)
-      acc = fmaf(t[n], cosf(6.283185307179586f * (float)((k * n) % s.A) / (float)s.A), acc);
+      acc = fmaf(t[n], cos_hd(6.283185307179586f * (float)((k * n) % s.A) / (float)s.A), acc);
     g[k] = acc;
   }
 }
@@ -412,7 +412,7 @@ SRNN_HD void g_apply(const GCtx& x, const SV& a, const SV& t, SV out, const Appl
       for (int m = 0; m < s.P; ++m) {
         float acc = 0.f;
         for (int k = 0; k < s.A; ++k)
-          acc = fmaf(h[k], cosf(6.283185307179586f * (float)((k * m) % s.P) / (float)s.P), acc);
+          acc = fmaf(h[k], cos_hd(6.283185307179586f * (float)((k * m) % s.P) / (float)s.P), acc);
         out[m] = acc / (float)s.P;
       }
     }
@@ -2171,6 +2171,376 @@ static int ww_launch(int op, const GShape& s, const WWave& g, const SrnnArgs& a)
   return 0;
 }
 
+// ==================================================================================
+// Reference-order generation of runtime shapes (OP_SOUP_ORDERED / OP_ORD_PLAN): the
+// continuation-scheduled generation of srnn_ordered.h with a lane-per-particle turn of this
+// engine.  The schedule (plan, mark, count, records, k_ord_run) is shape independent; this
+// file supplies the turn (GOrd: GItem::soup_seq_one reading the versions of its plan), the
+// run policy (GOrdPol) and the close (k_gord_close).
+//
+// Recompute depth 0: every attack output that a later turn or the close reads is a stored
+// version (W3) and its attacker a producer, so a turn needs only the three row vectors the
+// scratch already has (o_w, o_t, o_o; g_apply keeps o_f for its shuffle).  Depth 1 would add
+// two row vectors per lane.
+//
+// Scratch of a device generation: [GORD_HDR bytes: the GShape, written by k_gord_head -- the
+// run kernel's arguments are the template engines' (SrnnCfg, SrnnArgs)] [the lanes' element-
+// major vectors] [the lanes' orthogonal-init doubles].  The run launch has one lane per turn
+// plus the critical-list waves: srnn_ord_run_lanes(n), not the grid-stride cap of the other
+// operators.
+// ==================================================================================
+constexpr int GORD_RB = 0;
+constexpr int GORD_MAXP = 1024;      // Weightwise coordinate table in static LDS: 12 KB per workgroup
+constexpr int64_t GORD_HDR = 2048;   // bytes at the head of the scratch: the GShape
+static_assert(sizeof(GShape) <= (size_t)GORD_HDR, "the shape fits the scratch header");
+
+SRNN_HD void g_make_coords(const GShape& s, float* c) {
+  int k = 0;
+  for (int l = 0; l < s.NL; ++l)
+    for (int i = 0; i < s.rows[l]; ++i)
+      for (int j = 0; j < s.cols[l]; ++j) {
+        c[3 * k + 0] = norm_id(l, s.NL - 1);
+        c[3 * k + 1] = norm_id(i, s.rows[l] - 1);
+        c[3 * k + 2] = norm_id(j, s.cols[l] - 1);
+        ++k;
+      }
+}
+
+// lanes of the run launch of n turns: the turn waves and as many critical-list waves as
+// ord_run_args may ask for (SRNN_KNOB_ORD_CRIT)
+static int64_t gord_run_lanes(int64_t n) {
+  const int64_t nb = (n + TB - 1) / TB;
+  return (nb + std::min<int64_t>(nb, (ord::rec_total(n) + TB - 1) / TB)) * TB;
+}
+static int64_t gord_scratch_bytes(const GShape& s, int64_t n) {
+  return GORD_HDR + std::max<int64_t>(gord_run_lanes(n), GTB) * g_lane_bytes(s);
+}
+SRNN_HD void* gord_lanes_base(const SrnnArgs& a) { return reinterpret_cast<char*>(a.scratch) + GORD_HDR; }
+
+struct GOrd : ord::OrdSched<GORD_RB> {
+  using Sched = ord::OrdSched<GORD_RB>;
+  static constexpr int RB = GORD_RB;
+
+  SRNN_HD static void read_version(const GShape& s, const SrnnArgs& a, int32_t code, SV w) {
+    // a code that names no row (SRC_SELF / SRC_ATK / SRC_NONE where the turn's decisions ask for a
+    // row): the plan does not belong to this generation -- it was overwritten under the running turns,
+    // which only a counter-ordered plan whose wait gave up can do (SRNN_F_ORD_SYNC, ord::sync_wait).
+    // Nothing is read (the row index would be ~2^31); the generation is wrong and says so.
+    if ((code >= 0 ? (int64_t)(code >> 1) : -(int64_t)code - 1) >= a.n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      atomicOr(a.o_ctl + ord::ERRW, ord::ERR_SYNC);
+#else
+      __atomic_fetch_or(a.o_ctl + ord::ERRW, ord::ERR_SYNC, __ATOMIC_RELAXED);
+#endif
+      return;
+    }
+    if (code >= 0) {
+      const int64_t j = code >> 1;
+      g_load(s, (code & 1) ? GItem::rowp(s, a.W, j) : GItem::rowp(s, a.W3, j), w);
+    } else {
+      g_load(s, GItem::rowp(s, a.W2, (int64_t)(-(int64_t)code - 1)), w);
+    }
+  }
+  // version `code` into w (depth 0: every version read is a stored one)
+  template <int B>
+  SRNN_HD static void mat(const GShape& s, const SrnnArgs& a, int32_t code, SV w) {
+    static_assert(B == 0, "a recompute of attack outputs needs two more row vectors per depth");
+    read_version(s, a, code, w);
+  }
+
+  // turn k: GItem::soup_seq_one reading the versions of its plan
+  SRNN_HD static void turn(const GCtx& x, const SrnnArgs& a, int64_t k, int32_t gen) {
+    const GShape& s = *x.s;
+    const int32_t* sc = a.o_src + 4 * k;
+    SV w = x.v(s.o_w), f = x.v(s.o_t), o = x.v(s.o_o);
+    int64_t at, te;
+    Dec::decision(a, k, gen, at, te);
+    mat<RB>(s, a, sc[0], w);
+    int8_t act = A_NONE;
+    int64_t cp = -1;
+    if (at >= 0) {  // 1. attack: the victim's row becomes f_k(victim) (A(k))
+      if (ord::needs_A(a, k, sc)) {
+        if (at == k) g_copy(s, f, w);
+        else mat<RB>(s, a, sc[1], f);
+        g_apply(x, w, f, o, GItem::actx(a, s, (uint64_t)k, (uint32_t)gen * 1024u + 1u));
+        g_quant(s, o);
+        if (ord::stored(a, k)) g_store(s, GItem::rowp(s, a.W3, k), o);
+        if (at == k) g_copy(s, w, o);
+      }
+      act = A_ATTACKING;
+      cp = at;
+    }
+    TrainCtx tc = GItem::tctx(a, s, (uint64_t)k, (uint32_t)gen * 1024u + 512u);
+    float loss = 0.f;
+    if (te >= 0) {  // 2. learn_from the teacher's current row
+      if (sc[2] == ord::SRC_SELF) g_copy(s, f, w);
+      else if (sc[2] == ord::SRC_ATK) g_copy(s, f, o);
+      else mat<RB>(s, a, sc[2], f);
+      if (a.severity > 0) loss = g_train_epochs(x, w, f, a.severity, false, tc);
+      act = A_LEARN_FROM;
+      cp = te;
+    }
+    if (a.epochs > 0) {  // 3. self-train
+      loss = g_train_epochs(x, w, f, a.epochs, true, tc);
+      act = A_TRAIN_SELF;
+      cp = -1;
+    }
+    g_quant(s, w);  // 4. respawn (the stored state decides)
+    int8_t rs = 0;
+    if ((a.flags & SRNN_F_REMOVE_DIVERGENT) && g_diverged(s, w)) rs = 1;
+    else if ((a.flags & SRNN_F_REMOVE_ZERO) && g_zero(s, w, a.eps)) rs = 2;
+    if (a.traj) g_store(s, GItem::rowp(s, a.traj, k), w);  // recording: the state before any respawn
+    if (rs) g_init(x, w, GItem::rng(a), respawn_key(gen, k));
+    g_store(s, GItem::rowp(s, a.W, k), w);  // E(k)
+    if (a.action) a.action[k] = act;
+    if (a.counterpart) a.counterpart[k] = cp;
+    if (a.loss) a.loss[k] = loss;
+    if (a.respawn) a.respawn[k] = rs;
+  }
+
+  // row r after the generation: the last attack after its own turn, else E(r) (in W);
+  // consumes r's attack list; w receives the final row
+  SRNN_HD static void close_row(const GCtx& x, const SrnnArgs& a, int64_t r, SV w) {
+    const GShape& s = *x.s;
+    const int64_t ja = ord::last_attacker_before(a, r, a.n);
+    a.heads[r] = SRNN_NIL;  // consumed: NIL for the generation after next
+    if (ja > r) {
+      mat<RB>(s, a, ord::code_A(ja), w);
+      g_store(s, GItem::rowp(s, a.W, r), w);
+    } else {
+      g_load(s, GItem::rowp(s, a.W, r), w);
+    }
+  }
+};
+
+// the run policy of k_ord_run: the shape from the scratch header, the lane's slice of the
+// scratch (stride: the turn lanes of the launch), the Weightwise coordinate table in LDS.
+// A turn is entered by any subset of the wave's lanes, so every lane writes the whole table
+// before it reads it (the same values to the same words; a turn's training dwarfs the 3 P stores).
+struct GOrdPol {
+  static constexpr bool SHADOW = false;  // (a shadow lane would share its owner's scratch slice)
+  static constexpr bool CENSUS = false;  // (the census stays in the close)
+  static constexpr int RB = GORD_RB;
+  using PT = void;  // no permutation table
+  struct Shared {
+    float coords[3 * GORD_MAXP];
+  };
+  __device__ static void turn(const SrnnCfg&, const SrnnArgs& a, int64_t k, int32_t gen, Shared& sh, int64_t) {
+    const GShape& s = *reinterpret_cast<const GShape*>(a.scratch);
+    if (s.kind == 0) g_make_coords(s, sh.coords);
+    const int64_t lanes = (((a.flags & SRNN_F_ORD_CRIT) ? a.x_groups : 0) + (a.n + TB - 1) / TB) * TB;
+    const int64_t L = (int64_t)blockIdx.x * TB + threadIdx.x;
+    void* base = gord_lanes_base(a);
+    GCtx x{&s, reinterpret_cast<float*>(base) + L, lanes, sh.coords, g_orth(s, base, lanes, L)};
+    GOrd::turn(x, a, k, gen);
+  }
+};
+
+// the shape into the scratch header (before the run launch, on its stream)
+__global__ void k_gord_head(GShape s, SrnnArgs a) {
+  int32_t* d = reinterpret_cast<int32_t*>(a.scratch);
+  const int32_t* src = reinterpret_cast<const int32_t*>(&s);
+  for (int i = threadIdx.x; i < (int)(sizeof(GShape) / 4); i += blockDim.x) d[i] = src[i];
+}
+
+// final rows, census, next decisions, block stats (k_ord_close with the runtime-shape row code)
+__global__ __launch_bounds__(TB) void k_gord_close(GShape s, SrnnArgs a) {
+  using Dec = GOrd::Dec;
+  __shared__ float s_coords[3 * GORD_MAXP];
+  if (s.kind == 0) make_coords_dev(s, s_coords);
+  const int64_t gb = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int64_t r = gb * TB + lane, lanes = (int64_t)gridDim.x * TB;
+  void* base = gord_lanes_base(a);
+  GCtx x{&s, reinterpret_cast<float*>(base) + r, lanes, s_coords, g_orth(s, base, lanes, r)};
+  const int32_t gen = Dec::gen_of(a);
+  const bool census = (a.flags & SRNN_F_FUSED_CENSUS) != 0;
+  // (in-run planning: this set's barrier counter is free for the plan two generations on)
+  if ((a.flags & SRNN_F_ORD_INPLAN) && gb == 0 && lane == 0) a.o_ctl[ord::BARW] = 0;
+  bool rs = false;
+  int8_t k = -1;
+  if (r < a.n) {
+    if (a.o_src[4 * r + 3] < 0) atomicOr(a.o_ctl + ord::ERRW, ord::ERR_NOT_RUN);  // never ran: a scheduling bug
+    SV w = x.v(s.o_w);
+    GOrd::close_row(x, a, r, w);
+    rs = a.respawn[r] != 0;
+    if (!(a.flags & SRNN_F_ORD_PLANNED)) {  // (planned ahead: the next OP_ORD_PLAN links them)
+      int64_t at, te;
+      Dec::decision(a, r, gen + 1, at, te);
+      if (at >= 0) Dec::link(a.heads_next, a.nexts_next, at, (uint32_t)r);
+    }
+    if (census)
+      k = g_classify_w(x, w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, GItem::actx(a, s, (uint64_t)r, 0x7FFFFFF0u));
+  }
+  if ((a.flags & SRNN_F_GEN_COUNTS) && gb == 0 && lane == 0) Dec::set_gen(a, gen + 1);
+  const unsigned long long m = __ballot(rs);
+  uint32_t cnt[5];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) cnt[q] = (uint32_t)__popcll(__ballot(k == q));
+  if (lane == 0) {
+    unsigned long long* bs = reinterpret_cast<unsigned long long*>(a.temp);
+    unsigned long long* mine = bs + gb * 4;
+    mine[0] = m;
+    mine[1] = (unsigned long long)cnt[0] | ((unsigned long long)cnt[1] << 32);
+    mine[2] = (unsigned long long)cnt[2] | ((unsigned long long)cnt[3] << 32);
+    mine[3] = (unsigned long long)cnt[4];
+    if ((a.flags & SRNN_F_BORN_TOTAL) && m) atomicAdd(bs + ((a.n + TB - 1) / TB) * 4, (unsigned long long)__popcll(m));
+  }
+  // SRNN_F_ORD_SYNC: the launch ends (and the next run starts) once the next generation's plan is done
+  if ((a.flags & SRNN_F_ORD_SYNC) && gb == 0 && lane == 0)
+    ord::sync_wait(a.o_sync, ord::SYNC_CLOSE, ord::SYNC_PLAN, a.o_ctl + ord::ERRW);
+}
+
+// which runtime shapes have a reference-order generation: every valid shape on the device whose
+// Weightwise coordinate table fits the run launch's static LDS; on the host every shape but the
+// big aggregating nets (aggregating, P > 64: they have no host form)
+static bool gord_serves(const GShape& s, int op, bool dev, const char** why) {
+  if (!dev && s.kind == 1 && s.P > 64) {
+    *why = "the big aggregating nets (aggregating, P > 64) have no host reference-order generation";
+    return false;
+  }
+  if (dev && op == OP_SOUP_ORDERED && s.kind == 0 && s.P > GORD_MAXP) {
+    *why = "device reference-order generation of a runtime shape: the Weightwise coordinate table (3 P floats) "
+           "must fit the run launch's static LDS (P <= 1024)";
+    return false;
+  }
+  return true;
+}
+
+// OP_ORD_PLAN of a runtime shape (shape independent, recompute depth GORD_RB)
+static int g_ord_plan(const SrnnCfg& c, const SrnnArgs& a) {
+  if (!ord_single_table(a)) return -5;
+  if (!a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts) {
+    set_error("ordered generation plan needs o_src, o_list, o_ctl and the planned generation's (NIL) attack lists");
+    return -5;
+  }
+  if ((a.flags & SRNN_F_ORD_SYNC) && (!a.dev || !a.o_sync || !(a.flags & SRNN_F_ORD_NEXT))) {
+    set_error("SRNN_F_ORD_SYNC: a device plan of the next generation with the o_sync counters");
+    return -5;
+  }
+  if (!a.dev) {
+    ord_plan_host<GORD_RB>(a, true);
+    return 0;
+  }
+  ord_plan_dev<GORD_RB, void>(c, a, true);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error(hipGetErrorString(e));
+    return -3;
+  }
+  return 0;
+}
+
+// OP_SOUP_ORDERED of a runtime shape: soup_ordered's argument checks, host branch and launch
+// sequence (srnn_ordered.h) with this engine's turn, close and scratch
+static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) {
+  using Dec = GOrd::Dec;
+  const bool planned = (a.flags & SRNN_F_ORD_PLANNED) != 0;
+  if (!ord_single_table(a)) return -5;
+  if (!a.W || !a.W2 || !a.W3 || !a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts ||
+      (!planned && (!a.heads_next || !a.nexts_next)) || !a.respawn || a.o_levels < 1 ||
+      a.o_levels > ord::MAX_LEVELS) {
+    set_error("ordered soup generation needs W, W2, W3, o_src, o_list, o_ctl, the attack lists (both unless "
+              "planned ahead), respawn and 1 <= o_levels <= 16");
+    return -5;
+  }
+  if (!ord_inplan_ok(a) || !ord_sync_ok(a) || !ord_census_later_ok(a)) return -5;
+  if (a.o_census_temp || (a.flags & SRNN_F_ORD_CENSUS_LATER)) {
+    set_error("runtime-shape ordered generation: the census stays in the close (no o_census_temp, no "
+              "SRNN_F_ORD_CENSUS_LATER: OP_ORD_CENSUS has no runtime-shape form)");
+    return -5;
+  }
+  if (!a.dev) {
+    const int32_t gen = Dec::gen_of(a);
+    if (!planned) ord_plan_host<GORD_RB>(a, false);
+    std::vector<float> coords((size_t)(3 * s.P + 3));
+    if (s.kind == 0) make_coords_host(s, coords.data());
+    auto with_ctx = [&](auto&& f) {  // each worker its own stride-1 scratch
+      return [&, f](int64_t i) {
+        thread_local std::vector<float> buf;
+        thread_local std::vector<double> orth;
+        if (buf.size() < (size_t)s.sfloats) buf.resize((size_t)s.sfloats);
+        if (orth.size() < (size_t)s.orthd + 1) orth.resize((size_t)s.orthd + 1);
+        GCtx x{&s, buf.data(), 1, coords.data(), orth.data()};
+        f(x, i);
+      };
+    };
+    // levels in index order (every producer precedes its consumer)
+    std::vector<std::vector<int64_t>> lists;
+    for (int64_t k = 0; k < a.n; ++k) {
+      const int32_t lv = a.o_src[4 * k + 3];
+      if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
+      lists[(size_t)lv].push_back(k);
+    }
+    for (const auto& li : lists)
+      host_parallel((int64_t)li.size(), with_ctx([&](const GCtx& x, int64_t q) { GOrd::turn(x, a, li[(size_t)q], gen); }));
+    std::vector<int8_t> ks((size_t)a.n, (int8_t)-1);
+    const bool census = (a.flags & SRNN_F_FUSED_CENSUS) != 0;
+    host_parallel(a.n, with_ctx([&](const GCtx& x, int64_t r) {
+      SV w = x.v(s.o_w);
+      GOrd::close_row(x, a, r, w);
+      if (census)
+        ks[(size_t)r] = g_classify_w(x, w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0,
+                                     GItem::actx(a, s, (uint64_t)r, 0x7FFFFFF0u));
+    }));
+    if (!planned)
+      for (int64_t r = 0; r < a.n; ++r) {
+        int64_t at, te;
+        Dec::decision(a, r, gen + 1, at, te);
+        if (at >= 0) {
+          a.nexts_next[r] = a.heads_next[at];
+          a.heads_next[at] = (uint32_t)r;
+        }
+      }
+    // the finish inline: uids in slot order, census, counter
+    uint64_t cs[5] = {0, 0, 0, 0, 0};
+    for (int64_t r = 0; r < a.n; ++r)
+      if (ks[(size_t)r] >= 0) cs[ks[(size_t)r]]++;
+    int64_t u = a.uid_base ? a.uid_base[0] : 0, total = 0;
+    for (int64_t r = 0; r < a.n; ++r)
+      if (a.respawn[r]) {
+        if (a.uid_out) a.uid_out[r] = u;
+        ++u;
+        ++total;
+      }
+    if (a.uid_base) a.uid_base[0] = u;
+    Dec::set_gen(a, gen + 1);
+    if (a.counts) {
+      for (int q = 0; q < 5; ++q) a.counts[q] = census ? cs[q] : 0;
+      a.counts[5] = (uint64_t)total;
+    }
+    if (a.flags & SRNN_F_ORD_INPLAN) ord_plan_host<GORD_RB>(ord_next_plan_args(a), true);  // the next plan
+    return 0;
+  }
+  if (!(a.flags & SRNN_F_TWO_PHASE) || !a.temp) {
+    set_error("device ordered soup generation: two-phase block stats (temp) needed");
+    return -5;
+  }
+  if (!a.scratch || a.scratch_bytes < gord_scratch_bytes(s, a.n)) {
+    set_error("runtime-shape ordered generation: scratch missing or shorter than the run launch needs (one lane per "
+              "turn plus the critical-list waves: srnn_generic_ord_scratch_bytes)");
+    return -5;
+  }
+  const int64_t nb = (a.n + TB - 1) / TB;
+  if (nb <= 0) return 0;
+  hipStream_t st = (hipStream_t)a.stream;
+  if (!planned) ord_plan_dev<GORD_RB, void>(c, a, false);
+  const SrnnArgs ra = ord_run_args(a, nb);
+  hipLaunchKernelGGL(k_gord_head, dim3(1), dim3(64), 0, st, s, a);
+  hipLaunchKernelGGL((k_ord_run<GOrdPol>), dim3((unsigned)ord_run_grid(ra, nb)), dim3(TB), 0, st, c, ra);
+  hipLaunchKernelGGL(k_gord_close, dim3((unsigned)nb), dim3(TB), 0, st, s, a);
+  if (!(a.flags & SRNN_F_GEN_COUNTS)) {
+    constexpr int FNT = SRNN_FINISH_NT;
+    hipLaunchKernelGGL((k_gen_finish<Weightwise<1, 1>, StF32, FNT>), dim3(1), dim3(FNT), 0, st, a, (int32_t)nb);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error(hipGetErrorString(e));
+    return -3;
+  }
+  return 0;
+}
+
 // lanes of a device launch and the scratch bytes they need
 static int64_t generic_lanes(const GShape& s, const SrnnArgs& a, int64_t items) {
   const int64_t per = g_lane_bytes(s);
@@ -2263,6 +2633,17 @@ extern "C" int srnn_dispatch_generic(int op, const SrnnCfg* c, const SrnnArgs* a
     srnn::host_generic(op, s, *a);
     return 0;
   }
+  if (op == OP_SOUP_ORDERED || op == OP_ORD_PLAN) {  // the reference order, scheduled (host and device)
+    if (!srnn::gord_serves(s, op, a->dev != 0, &why)) {
+      srnn::set_error(why);
+      return -5;
+    }
+    return op == OP_ORD_PLAN ? srnn::g_ord_plan(*c, *a) : srnn::g_soup_ordered(*c, s, *a);
+  }
+  if (op == OP_GEN_FINISH) {  // shape independent: the batched / serial finish of srnn_kernels.h
+    SrnnCfg dummy{};
+    return srnn::gen_finish<srnn::Weightwise<1, 1>, srnn::StF32>(dummy, *a);
+  }
   if (!srnn::generic_op_supported(op)) return 2;
   if (!a->dev) {
     if (op == OP_SOUP_DECIDE) {
@@ -2285,4 +2666,25 @@ extern "C" int64_t srnn_generic_scratch_bytes(const SrnnCfg* c, int64_t n, int64
   if (max_lanes > 0 && lanes > max_lanes) lanes = (max_lanes / srnn::GTB) * srnn::GTB;
   if (lanes < srnn::GTBR) lanes = srnn::GTBR;
   return lanes * srnn::g_lane_bytes(s);
+}
+
+// Lanes of the run launch of a reference-order generation of n turns (one per turn plus the
+// critical-list waves), and the scratch bytes OP_SOUP_ORDERED of a runtime shape needs on the
+// device for them (header included; -1: not a valid shape)
+extern "C" int64_t srnn_ord_run_lanes(int64_t n) { return srnn::gord_run_lanes(n < 0 ? 0 : n); }
+extern "C" int64_t srnn_generic_ord_scratch_bytes(const SrnnCfg* c, int64_t n) {
+  srnn::GShape s;
+  const char* why = "";
+  if (!srnn::make_gshape(*c, s, &why)) return -1;
+  return srnn::gord_scratch_bytes(s, n < 0 ? 0 : n);
+}
+
+// 1 when the runtime-shape engine serves `op` of this configuration on the host (dev 0) / device
+// (dev 1): srnn_generic_op_supported, and the reference-order generation with the shape in hand
+extern "C" int srnn_generic_supports(const SrnnCfg* c, int op, int dev) {
+  if (op != OP_SOUP_ORDERED && op != OP_ORD_PLAN) return srnn_generic_op_supported(op, dev);
+  srnn::GShape s;
+  const char* why = "";
+  if (!srnn::make_gshape(*c, s, &why)) return 0;
+  return srnn::gord_serves(s, op, dev != 0, &why) ? 1 : 0;
 }

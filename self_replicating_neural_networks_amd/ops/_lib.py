@@ -196,6 +196,10 @@ def lib():
         L.srnn_supports.restype = ctypes.c_int
         L.srnn_generic_scratch_bytes.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int64, ctypes.c_int64]
         L.srnn_generic_scratch_bytes.restype = ctypes.c_int64
+        L.srnn_ord_run_lanes.argtypes = [ctypes.c_int64]
+        L.srnn_ord_run_lanes.restype = ctypes.c_int64
+        L.srnn_generic_ord_scratch_bytes.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int64]
+        L.srnn_generic_ord_scratch_bytes.restype = ctypes.c_int64
         L.srnn_big_fix_temp_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
         L.srnn_big_fix_temp_bytes.restype = ctypes.c_int64
         L.srnn_set_force_generic.argtypes = [ctypes.c_int]
@@ -327,6 +331,18 @@ def set_ww_wave(on: bool) -> None:
 def generic_scratch_bytes(spec, n: int, dtype: int = DTYPE_FP32, max_lanes: int = 65536) -> int:
     """Device scratch the runtime-shape engine needs for ``n`` rows (per-lane vectors)."""
     return int(lib().srnn_generic_scratch_bytes(ctypes.byref(make_cfg(spec, dtype)), int(n), int(max_lanes)))
+
+
+def ord_run_lanes(n: int) -> int:
+    """Lanes of the run launch of an ``n``-turn reference-order generation: one per turn plus the
+    critical-list waves (csrc/srnn_generic.hip gord_run_lanes)."""
+    return int(lib().srnn_ord_run_lanes(int(n)))
+
+
+def generic_ord_scratch_bytes(spec, n: int, dtype: int = DTYPE_FP32) -> int:
+    """Device scratch OP_SOUP_ORDERED of a runtime shape needs for ``n`` turns: the shape header and
+    the per-lane vectors of every lane of the run launch (``ord_run_lanes``)."""
+    return int(lib().srnn_generic_ord_scratch_bytes(ctypes.byref(make_cfg(spec, dtype)), int(n)))
 
 
 def big_fix_temp_bytes(spec, n: int, steps: int = 0, dense: bool = False) -> int:

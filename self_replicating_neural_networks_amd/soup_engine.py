@@ -209,6 +209,11 @@ def engine_bytes(spec: ArchSpec, n_total: int, world: int = 1, dtype=torch.float
             b += sharded_ordered_bytes(spec, n_total, R, dtype)
         else:
             b += ordered_bytes(spec, n, dtype, epochs, plan_sets=2 if ord_pipeline else 1)
+            dc = K.dtype_code(dtype)
+            if _lib.is_generic(spec, _lib.OP_SOUP_ORDERED, dc):
+                # a runtime shape: the scratch lanes of the run launch (a device buffer), shared with the
+                # engine's other runtime-shape operators
+                b += max(_lib.generic_scratch_bytes(spec, n, dc), _lib.generic_ord_scratch_bytes(spec, n, dc))
     return int(b)
 
 
@@ -276,7 +281,7 @@ class SoupEngine:
         and kernel families (config.ExecConfig; its environment variables override it);
         ``order``: ``"sequential"`` -- the reference's in-place, index-ordered generation
         (code/soup.py:51-87) scheduled by dependency level on the device (OP_SOUP_ORDERED,
-        bitwise the serial loop; single rank, lane-template shapes) -- or ``"synchronous"``
+        bitwise the serial loop; template shapes, and runtime shapes on a single rank) -- or ``"synchronous"``
         (Jacobi: every read from the generation-start table; any shape, sharded)."""
         if order not in ("synchronous", "sequential"):
             raise ValueError(f"order must be 'synchronous' or 'sequential', got {order!r}")
@@ -340,10 +345,18 @@ class SoupEngine:
         n_links = self.n_total if (self.dist.enabled and not self.x2) else self.n
         self.heads = [torch.full((self.n,), -1, **i32) for _ in range(2)]
         self._lists_ready = False   # heads[_p] already holds this generation's attacks
+        # the reference order of a runtime shape (csrc/srnn_generic.hip GOrd): block stats and finish as
+        # the template shapes' generation; its run launch has one scratch lane per turn (plus the
+        # critical-list waves), allocated here -- never inside a call, generations are graph-captured
+        self._ord_generic = (order == "sequential" and not self.dist.enabled
+                             and _lib.is_generic(spec, _lib.OP_SOUP_ORDERED, self.dtype_code))
         self._scratch = None
-        if self.device.type == "cuda" and _lib.is_generic(spec, _lib.OP_SOUP_EVOLVE, self.dtype_code):
-            self._scratch = torch.empty(_lib.generic_scratch_bytes(spec, self.n, self.dtype_code),
-                                        dtype=torch.uint8, device=dev)
+        if self.device.type == "cuda" and (self._ord_generic
+                                           or _lib.is_generic(spec, _lib.OP_SOUP_EVOLVE, self.dtype_code)):
+            nbytes = _lib.generic_scratch_bytes(spec, self.n, self.dtype_code)
+            if self._ord_generic:
+                nbytes = max(nbytes, _lib.generic_ord_scratch_bytes(spec, self.n, self.dtype_code))
+            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.ballots = torch.zeros(nb, **i64)       # respawn ballot per 64-row block (unfused evolve)
         self.rowflags = None                          # per-row respawn flags (all-gather exchange)
         self.err = torch.zeros(1, **i32)              # exchange error bits (X2_ERRORS)
@@ -400,7 +413,8 @@ class SoupEngine:
         i32 = dict(dtype=torch.int32, device=dev)
         # one launch (+ a one-workgroup finish) per generation: OP_SOUP_GEN; shapes without a
         # templated kernel run on the runtime-shape engine: decide -> evolve -> respawn -> census
-        self.fused = not self.dist.enabled and not self.generic
+        # (a runtime shape's reference-order generation writes the same block stats: finished alike)
+        self.fused = not self.dist.enabled and (not self.generic or self._ord_generic)
         self._blockstat = torch.zeros(nb * 8, **i32)  # u64[4] per 64-row block
         self._done = torch.zeros(1, **i32)
         # where the finish of a single-rank fused generation on a GPU runs (census reduction +
@@ -470,7 +484,8 @@ class SoupEngine:
         if not _lib.supports(self.spec, _lib.OP_SOUP_ORDERED, dev_side, self.dtype_code):
             raise NotImplementedError(
                 f"no scheduled reference-order generation for {self.spec} on {self.device.type}: it exists for "
-                "the lane-per-particle template shapes (host and device) and the big aggregating nets (device, "
+                "every shape on the device (runtime shapes: Weightwise nets up to 1024 weights, csrc/srnn_generic.hip) "
+                "and on the host for every shape but the big aggregating nets (aggregating, P > 64: device only, "
                 "csrc/srnn_bignet.h); SequentialSoupEngine runs the same order for any shape on the host, "
                 "SoupEngine(order='synchronous') any shape on the device")
         sharded = self.dist.enabled
@@ -520,7 +535,11 @@ class SoupEngine:
                 # (ord_graph_sync: the side stream's multi-generation graphs wait on the main stream's
                 # counters and the other way round -- the two streams must not share a hardware queue;
                 # the high-priority one is drawn from a queue pool of its own)
-                self._ord_decouple = bool(self.execution.ord_graph_sync)
+                # (a runtime shape keeps one-graph chunks: the counter waits give up after ~2 s (csrc
+                # ord::sync_wait), a bound a 100k-particle generation of a wide runtime shape passes -- its
+                # next-but-one plan would then overwrite the plan of the turns still running; and the join a
+                # two-graph chunk saves is ~10 us of a generation that takes milliseconds)
+                self._ord_decouple = bool(self.execution.ord_graph_sync) and not self._ord_generic
                 self._ord_side = torch.cuda.Stream(dev, priority=-1 if self._ord_decouple else 0)
                 self._osync = torch.zeros(4, dtype=torch.int32, device=dev)  # csrc ord::SYNC_*
         # (stream mode) the census of a generation's final rows runs on the side stream beside the

@@ -1826,7 +1826,8 @@ __global__ __launch_bounds__(TBR) void k_big_respawn_seq(SrnnCfg c, SrnnArgs a) 
 // ------------------------------------------------------------------ reference order
 // The reference's in-place, index-ordered generation (code/soup.py:51-87) of a big
 // aggregating net on the continuation scheduler of srnn_ordered.h (plan / mark / count / run
-// are shape independent; this is the turn and the close).  Recompute depth 1: an unstored
+// are shape independent; this is the turn, and the policy BigOrdPol of k_ord_run and
+// k_ord_close with the family's final-row code).  Recompute depth 1: an unstored
 // attack output A(j) is its attacker's forward on its victim's aggregate, and an aggregating
 // net's output is chunk-constant (shuffled: a permutation of the chunk values), so a version
 // read is either a streamed row or a 4-value chunk state -- the turn's own row is the only
@@ -2017,7 +2018,7 @@ struct BigOrd : ord::OrdSched<1> {
     if (a.respawn) a.respawn[k] = rsp;
   }
 };
-// the run policy of k_ord_run: the chunk ids of the shuffled outputs in LDS (stride TBROW)
+// the policy of k_ord_run and k_ord_close: the chunk ids of the shuffled outputs in LDS (stride TBROW)
 template <class T, class S, bool SHUF>
 struct BigOrdPol {
   static constexpr bool SHADOW = false;  // (the turn's staged reads are wave-cooperative)
@@ -2030,95 +2031,43 @@ struct BigOrdPol {
   __device__ static void turn(const SrnnCfg& c, const SrnnArgs& a, int64_t k, int32_t gen, Shared& sh, int64_t) {
     BigOrd<T, S, SHUF>::turn(c, a, k, gen, ChunkPerm<T>{sh.cw + threadIdx.x, TB});
   }
-};
-// final rows (the last attack after a row's own turn, else its E version), the next
-// generation's lists, census of the stored rows, block stats (two-phase, as k_ord_close)
-template <class T, class S, bool SHUF>
-__global__ __launch_bounds__(TB) void k_ordbig_close(SrnnCfg c, SrnnArgs a) {
-  using R = BRow<T, S>;
-  using Dec = ord::OrdSched<1>::Dec;
-  __shared__ uint32_t s_cw[SHUF ? ChunkPerm<T>::NW * TB : 1];
-  const ChunkPerm<T> cp{s_cw + threadIdx.x, TB};
-  const int64_t gb = blockIdx.x;
-  const int64_t r = gb * TB + threadIdx.x;
-  const int lane = threadIdx.x;
-  const int32_t gen = a.gen_ptr ? a.gen_ptr[0] : a.gen;
-  const bool census = !SHUF && (a.flags & SRNN_F_FUSED_CENSUS) != 0;
-  if ((a.flags & SRNN_F_ORD_INPLAN) && gb == 0 && threadIdx.x == 0) a.o_ctl[ord::BARW] = 0;
-  bool rs = false;
-  int8_t k = -1;
-  // the E rows through the wave's staging area (coalesced passes, as the synchronous soup's
+  // the close (k_ord_close): row r's final version (the last attack after its own turn, else its
+  // E version) and the class of the stored row (the shuffled nets' census is not the close's).
+  // The E rows come through the wave's staging area (coalesced passes, as the synchronous soup's
   // census: a lane-per-row load touches 64 rows 1120 B apart per instruction)
-  __shared__ uint4 s_stg[R::G::WAVE_U4];
-  float w[T::P];
-  R::load_staged(a.W, r < a.n ? (int32_t)r : -1, w, s_stg);
-  if (r < a.n) {
-    if (a.o_src[4 * r + 3] < 0) atomicOr(a.o_ctl + ord::ERRW, ord::ERR_NOT_RUN);  // never ran: a scheduling bug
+  using CloseArg = SrnnCfg;
+  struct CloseShared {
+    uint4 stg[BRow<T, S>::G::WAVE_U4];
+    uint32_t cw[SHUF ? ChunkPerm<T>::NW * TB : 0];  // (no chunk ids, and no LDS for them, without shuffle)
+  };
+  __device__ __forceinline__ static int8_t close(const SrnnCfg& c, const SrnnArgs& a, int64_t r, bool valid, int32_t gen,
+                                                 CloseShared& sh) {
+    using R = BRow<T, S>;
+    float w[T::P];
+    R::load_staged(a.W, valid ? (int32_t)r : -1, w, sh.stg);
+    if (!valid) return -1;
     const int64_t ja = ord::last_attacker_before(a, r, a.n);
     a.heads[r] = SRNN_NIL;  // consumed: NIL for the generation after next
     if (ja > r) {  // attacked after its own turn: the last attack's output
-      BigOrd<T, S, SHUF>::load_version(c, a, ord::code_A(ja), gen, cp, w);
+      BigOrd<T, S, SHUF>::load_version(c, a, ord::code_A(ja), gen, ChunkPerm<T>{sh.cw + threadIdx.x, TB}, w);
       R::store(R::at(a.W, r), w);
     }
-    rs = a.respawn[r] != 0;
-    if (!(a.flags & SRNN_F_ORD_PLANNED)) {  // (planned ahead: the next OP_ORD_PLAN links them)
-      int64_t at, te;
-      Dec::decision(a, r, gen + 1, at, te);
-      if (at >= 0) Dec::link(a.heads_next, a.nexts_next, at, (uint32_t)r);
-    }
-    if (census) k = sclassify<T, S>(w, RowSummary<T>(w), a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, c.aggregator);
+    if (SHUF || !(a.flags & SRNN_F_FUSED_CENSUS)) return -1;
+    return sclassify<T, S>(w, RowSummary<T>(w), a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, c.aggregator);
   }
-  if ((a.flags & SRNN_F_GEN_COUNTS) && gb == 0 && lane == 0) Dec::set_gen(a, gen + 1);
-  const unsigned long long m = __ballot(rs);
-  uint32_t cnt[5];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) cnt[q] = (uint32_t)__popcll(__ballot(k == q));
-  if (lane == 0) {
-    unsigned long long* bs = reinterpret_cast<unsigned long long*>(a.temp);
-    unsigned long long* mine = bs + gb * 4;
-    mine[0] = m;
-    mine[1] = (unsigned long long)cnt[0] | ((unsigned long long)cnt[1] << 32);
-    mine[2] = (unsigned long long)cnt[2] | ((unsigned long long)cnt[3] << 32);
-    mine[3] = (unsigned long long)cnt[4];
-    if ((a.flags & SRNN_F_BORN_TOTAL) && m) atomicAdd(bs + ((a.n + TB - 1) / TB) * 4, (unsigned long long)__popcll(m));
-  }
-  // SRNN_F_ORD_SYNC: the launch ends (and the next run starts) once the next generation's plan is done
-  if ((a.flags & SRNN_F_ORD_SYNC) && gb == 0 && lane == 0)
-    ord::sync_wait(a.o_sync, ord::SYNC_CLOSE, ord::SYNC_PLAN, a.o_ctl + ord::ERRW);
-}
-// OP_SOUP_ORDERED of a big aggregating net (device): soup_ordered's launch sequence with this
-// family's run policy and close (no permutation table: an aggregating net's SGD step has one
-// sample); the finish (uids, census, counter) follows unless the caller batches it
+};
+// OP_SOUP_ORDERED of a big aggregating net (device only): the shared checks and launch sequence
+// (srnn_ordered.h) with this family's policy; the census stays in the close
 template <class T, class S, bool SHUF>
 int big_soup_ordered(const SrnnCfg& c, const SrnnArgs& a) {
-  const bool planned = (a.flags & SRNN_F_ORD_PLANNED) != 0;
-  if (!ord_single_table(a)) return -5;
-  if (!a.W || !a.W2 || !a.W3 || !a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts ||
-      (!planned && (!a.heads_next || !a.nexts_next)) || !a.respawn || !(a.flags & SRNN_F_TWO_PHASE) || !a.temp) {
-    set_error("ordered soup generation needs W, W2, W3, o_src, o_list, o_ctl, the attack lists (both unless "
-              "planned ahead), respawn and two-phase block stats (temp)");
-    return -5;
-  }
-  if (!ord_inplan_ok(a) || !ord_sync_ok(a) || !ord_census_later_ok(a)) return -5;
+  if (!ord_generation_args_ok(a, false)) return -5;
   if (a.o_census_temp) {
     set_error("big ordered generation: no census in the run launch (o_census_temp)");
     return -5;
   }
-  const int64_t nb = (a.n + TB - 1) / TB;
-  if (nb <= 0) return 0;
-  hipStream_t st = (hipStream_t)a.stream;
-  if (!planned) ord_plan_dev<1, void>(c, a, false);
-  SrnnArgs ra = ord_run_args(a, nb);
   // (no head start for the critical roots by default: a 1M soup's bulk is the generation's work, and
   // delaying its first round cost 0.5-1.5 %, profiles/r6a r6n)
-  ra.o_bulk_delay = std::min(1000, std::max(0, knob(SRNN_KNOB_ORD_BULK_DELAY, 0)));
-  hipLaunchKernelGGL((k_ord_run<BigOrdPol<T, S, SHUF>>), dim3((unsigned)ord_run_grid(ra, nb)), dim3(TB), 0, st, c, ra);
-  hipLaunchKernelGGL((k_ordbig_close<T, S, SHUF>), dim3((unsigned)nb), dim3(TB), 0, st, c, a);
-  if (!(a.flags & SRNN_F_GEN_COUNTS)) {
-    constexpr int FNT = SRNN_FINISH_NT;
-    hipLaunchKernelGGL((k_gen_finish<Weightwise<1, 1>, StF32, FNT>), dim3(1), dim3(FNT), 0, st, a, (int32_t)nb);
-  }
-  return 0;
+  return ord_generation_dev<BigOrdPol<T, S, SHUF>>(c, c, a, 0, [](hipStream_t) {});
 }
 
 // ops of the big nets that take any storage format / shuffler (everything a soup needs)
@@ -2146,23 +2095,8 @@ int big_run_s(int op, const SrnnCfg& c, const SrnnArgs& a) {
       break;
     }
     case OP_RESPAWN_SEQ: hipLaunchKernelGGL((k_big_respawn_seq<T, S>), dim3(1), dim3(TBR), 0, st, c, a); break;
-    case OP_SOUP_ORDERED: {
-      const int r = big_soup_ordered<T, S, SHUF>(c, a);
-      if (r) return r;
-      break;
-    }
-    case OP_ORD_PLAN:  // (shape independent, recompute depth 1: soup_ord_plan's device path)
-      if (!ord_single_table(a)) return -5;
-      if (!a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts) {
-        set_error("ordered generation plan needs o_src, o_list, o_ctl and the planned generation's attack lists");
-        return -5;
-      }
-      if ((a.flags & SRNN_F_ORD_SYNC) && (!a.o_sync || !(a.flags & SRNN_F_ORD_NEXT))) {
-        set_error("SRNN_F_ORD_SYNC: a device plan of the next generation with the o_sync counters");
-        return -5;
-      }
-      ord_plan_dev<1, void>(c, a, true);
-      break;
+    case OP_SOUP_ORDERED: return big_soup_ordered<T, S, SHUF>(c, a);
+    case OP_ORD_PLAN: return ord_plan_op<1, void>(c, a, false);  // (no host form)
     case OP_SOUP_DECIDE: {
       // decisions are shape independent: every global slot
       if (a.n_total <= 0) return 0;

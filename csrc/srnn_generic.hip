@@ -2176,7 +2176,7 @@ static int ww_launch(int op, const GShape& s, const WWave& g, const SrnnArgs& a)
 // continuation-scheduled generation of srnn_ordered.h with a lane-per-particle turn of this
 // engine.  The schedule (plan, mark, count, records, k_ord_run) is shape independent; this
 // file supplies the turn (GOrd: GItem::soup_seq_one reading the versions of its plan), the
-// run policy (GOrdPol) and the close (k_gord_close).
+// policy of the run and the close (GOrdPol: k_ord_run<GOrdPol>, k_ord_close<GOrdPol>).
 //
 // Recompute depth 0: every attack output that a later turn or the close reads is a stored
 // version (W3) and its attacker a producer, so a turn needs only the three row vectors the
@@ -2313,8 +2313,9 @@ struct GOrd : ord::OrdSched<GORD_RB> {
   }
 };
 
-// the run policy of k_ord_run: the shape from the scratch header, the lane's slice of the
-// scratch (stride: the turn lanes of the launch), the Weightwise coordinate table in LDS.
+// the policy of k_ord_run and k_ord_close.  The run: the shape from the scratch header, the
+// lane's slice of the scratch (stride: the turn lanes of the launch), the Weightwise coordinate
+// table in LDS.
 // A turn is entered by any subset of the wave's lanes, so every lane writes the whole table
 // before it reads it (the same values to the same words; a turn's training dwarfs the 3 P stores).
 struct GOrdPol {
@@ -2334,6 +2335,22 @@ struct GOrdPol {
     GCtx x{&s, reinterpret_cast<float*>(base) + L, lanes, sh.coords, g_orth(s, base, lanes, L)};
     GOrd::turn(x, a, k, gen);
   }
+  // the close (k_ord_close): the shape is its first kernel argument, the lane's scratch slice
+  // has the stride of the close launch (one lane per row)
+  using CloseArg = GShape;
+  using CloseShared = Shared;
+  __device__ __forceinline__ static int8_t close(const GShape& s, const SrnnArgs& a, int64_t r, bool valid, int32_t,
+                                                 Shared& sh) {
+    if (s.kind == 0) make_coords_dev(s, sh.coords);
+    if (!valid) return -1;
+    const int64_t lanes = (int64_t)gridDim.x * TB;
+    void* base = gord_lanes_base(a);
+    GCtx x{&s, reinterpret_cast<float*>(base) + r, lanes, sh.coords, g_orth(s, base, lanes, r)};
+    SV w = x.v(s.o_w);
+    GOrd::close_row(x, a, r, w);
+    if (!(a.flags & SRNN_F_FUSED_CENSUS)) return -1;
+    return g_classify_w(x, w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, GItem::actx(a, s, (uint64_t)r, 0x7FFFFFF0u));
+  }
 };
 
 // the shape into the scratch header (before the run launch, on its stream)
@@ -2341,54 +2358,6 @@ __global__ void k_gord_head(GShape s, SrnnArgs a) {
   int32_t* d = reinterpret_cast<int32_t*>(a.scratch);
   const int32_t* src = reinterpret_cast<const int32_t*>(&s);
   for (int i = threadIdx.x; i < (int)(sizeof(GShape) / 4); i += blockDim.x) d[i] = src[i];
-}
-
-// final rows, census, next decisions, block stats (k_ord_close with the runtime-shape row code)
-__global__ __launch_bounds__(TB) void k_gord_close(GShape s, SrnnArgs a) {
-  using Dec = GOrd::Dec;
-  __shared__ float s_coords[3 * GORD_MAXP];
-  if (s.kind == 0) make_coords_dev(s, s_coords);
-  const int64_t gb = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int64_t r = gb * TB + lane, lanes = (int64_t)gridDim.x * TB;
-  void* base = gord_lanes_base(a);
-  GCtx x{&s, reinterpret_cast<float*>(base) + r, lanes, s_coords, g_orth(s, base, lanes, r)};
-  const int32_t gen = Dec::gen_of(a);
-  const bool census = (a.flags & SRNN_F_FUSED_CENSUS) != 0;
-  // (in-run planning: this set's barrier counter is free for the plan two generations on)
-  if ((a.flags & SRNN_F_ORD_INPLAN) && gb == 0 && lane == 0) a.o_ctl[ord::BARW] = 0;
-  bool rs = false;
-  int8_t k = -1;
-  if (r < a.n) {
-    if (a.o_src[4 * r + 3] < 0) atomicOr(a.o_ctl + ord::ERRW, ord::ERR_NOT_RUN);  // never ran: a scheduling bug
-    SV w = x.v(s.o_w);
-    GOrd::close_row(x, a, r, w);
-    rs = a.respawn[r] != 0;
-    if (!(a.flags & SRNN_F_ORD_PLANNED)) {  // (planned ahead: the next OP_ORD_PLAN links them)
-      int64_t at, te;
-      Dec::decision(a, r, gen + 1, at, te);
-      if (at >= 0) Dec::link(a.heads_next, a.nexts_next, at, (uint32_t)r);
-    }
-    if (census)
-      k = g_classify_w(x, w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, GItem::actx(a, s, (uint64_t)r, 0x7FFFFFF0u));
-  }
-  if ((a.flags & SRNN_F_GEN_COUNTS) && gb == 0 && lane == 0) Dec::set_gen(a, gen + 1);
-  const unsigned long long m = __ballot(rs);
-  uint32_t cnt[5];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) cnt[q] = (uint32_t)__popcll(__ballot(k == q));
-  if (lane == 0) {
-    unsigned long long* bs = reinterpret_cast<unsigned long long*>(a.temp);
-    unsigned long long* mine = bs + gb * 4;
-    mine[0] = m;
-    mine[1] = (unsigned long long)cnt[0] | ((unsigned long long)cnt[1] << 32);
-    mine[2] = (unsigned long long)cnt[2] | ((unsigned long long)cnt[3] << 32);
-    mine[3] = (unsigned long long)cnt[4];
-    if ((a.flags & SRNN_F_BORN_TOTAL) && m) atomicAdd(bs + ((a.n + TB - 1) / TB) * 4, (unsigned long long)__popcll(m));
-  }
-  // SRNN_F_ORD_SYNC: the launch ends (and the next run starts) once the next generation's plan is done
-  if ((a.flags & SRNN_F_ORD_SYNC) && gb == 0 && lane == 0)
-    ord::sync_wait(a.o_sync, ord::SYNC_CLOSE, ord::SYNC_PLAN, a.o_ctl + ord::ERRW);
 }
 
 // which runtime shapes have a reference-order generation: every valid shape on the device whose
@@ -2407,52 +2376,17 @@ static bool gord_serves(const GShape& s, int op, bool dev, const char** why) {
   return true;
 }
 
-// OP_ORD_PLAN of a runtime shape (shape independent, recompute depth GORD_RB)
-static int g_ord_plan(const SrnnCfg& c, const SrnnArgs& a) {
-  if (!ord_single_table(a)) return -5;
-  if (!a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts) {
-    set_error("ordered generation plan needs o_src, o_list, o_ctl and the planned generation's (NIL) attack lists");
-    return -5;
-  }
-  if ((a.flags & SRNN_F_ORD_SYNC) && (!a.dev || !a.o_sync || !(a.flags & SRNN_F_ORD_NEXT))) {
-    set_error("SRNN_F_ORD_SYNC: a device plan of the next generation with the o_sync counters");
-    return -5;
-  }
-  if (!a.dev) {
-    ord_plan_host<GORD_RB>(a, true);
-    return 0;
-  }
-  ord_plan_dev<GORD_RB, void>(c, a, true);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(hipGetErrorString(e));
-    return -3;
-  }
-  return 0;
-}
-
-// OP_SOUP_ORDERED of a runtime shape: soup_ordered's argument checks, host branch and launch
-// sequence (srnn_ordered.h) with this engine's turn, close and scratch
+// OP_SOUP_ORDERED of a runtime shape: the shared checks, host generation and launch sequence
+// (srnn_ordered.h) with this engine's turn, close and scratch
 static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) {
-  using Dec = GOrd::Dec;
-  const bool planned = (a.flags & SRNN_F_ORD_PLANNED) != 0;
-  if (!ord_single_table(a)) return -5;
-  if (!a.W || !a.W2 || !a.W3 || !a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts ||
-      (!planned && (!a.heads_next || !a.nexts_next)) || !a.respawn || a.o_levels < 1 ||
-      a.o_levels > ord::MAX_LEVELS) {
-    set_error("ordered soup generation needs W, W2, W3, o_src, o_list, o_ctl, the attack lists (both unless "
-              "planned ahead), respawn and 1 <= o_levels <= 16");
-    return -5;
-  }
-  if (!ord_inplan_ok(a) || !ord_sync_ok(a) || !ord_census_later_ok(a)) return -5;
+  if (!ord_generation_args_ok(a, true)) return -5;
   if (a.o_census_temp || (a.flags & SRNN_F_ORD_CENSUS_LATER)) {
     set_error("runtime-shape ordered generation: the census stays in the close (no o_census_temp, no "
               "SRNN_F_ORD_CENSUS_LATER: OP_ORD_CENSUS has no runtime-shape form)");
     return -5;
   }
   if (!a.dev) {
-    const int32_t gen = Dec::gen_of(a);
-    if (!planned) ord_plan_host<GORD_RB>(a, false);
+    const int32_t gen = GOrd::Dec::gen_of(a);
     std::vector<float> coords((size_t)(3 * s.P + 3));
     if (s.kind == 0) make_coords_host(s, coords.data());
     auto with_ctx = [&](auto&& f) {  // each worker its own stride-1 scratch
@@ -2462,83 +2396,27 @@ static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) 
         if (buf.size() < (size_t)s.sfloats) buf.resize((size_t)s.sfloats);
         if (orth.size() < (size_t)s.orthd + 1) orth.resize((size_t)s.orthd + 1);
         GCtx x{&s, buf.data(), 1, coords.data(), orth.data()};
-        f(x, i);
+        return f(x, i);
       };
     };
-    // levels in index order (every producer precedes its consumer)
-    std::vector<std::vector<int64_t>> lists;
-    for (int64_t k = 0; k < a.n; ++k) {
-      const int32_t lv = a.o_src[4 * k + 3];
-      if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
-      lists[(size_t)lv].push_back(k);
-    }
-    for (const auto& li : lists)
-      host_parallel((int64_t)li.size(), with_ctx([&](const GCtx& x, int64_t q) { GOrd::turn(x, a, li[(size_t)q], gen); }));
-    std::vector<int8_t> ks((size_t)a.n, (int8_t)-1);
-    const bool census = (a.flags & SRNN_F_FUSED_CENSUS) != 0;
-    host_parallel(a.n, with_ctx([&](const GCtx& x, int64_t r) {
-      SV w = x.v(s.o_w);
-      GOrd::close_row(x, a, r, w);
-      if (census)
-        ks[(size_t)r] = g_classify_w(x, w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0,
-                                     GItem::actx(a, s, (uint64_t)r, 0x7FFFFFF0u));
-    }));
-    if (!planned)
-      for (int64_t r = 0; r < a.n; ++r) {
-        int64_t at, te;
-        Dec::decision(a, r, gen + 1, at, te);
-        if (at >= 0) {
-          a.nexts_next[r] = a.heads_next[at];
-          a.heads_next[at] = (uint32_t)r;
-        }
-      }
-    // the finish inline: uids in slot order, census, counter
-    uint64_t cs[5] = {0, 0, 0, 0, 0};
-    for (int64_t r = 0; r < a.n; ++r)
-      if (ks[(size_t)r] >= 0) cs[ks[(size_t)r]]++;
-    int64_t u = a.uid_base ? a.uid_base[0] : 0, total = 0;
-    for (int64_t r = 0; r < a.n; ++r)
-      if (a.respawn[r]) {
-        if (a.uid_out) a.uid_out[r] = u;
-        ++u;
-        ++total;
-      }
-    if (a.uid_base) a.uid_base[0] = u;
-    Dec::set_gen(a, gen + 1);
-    if (a.counts) {
-      for (int q = 0; q < 5; ++q) a.counts[q] = census ? cs[q] : 0;
-      a.counts[5] = (uint64_t)total;
-    }
-    if (a.flags & SRNN_F_ORD_INPLAN) ord_plan_host<GORD_RB>(ord_next_plan_args(a), true);  // the next plan
+    ord_generation_host<GORD_RB>(
+        a, with_ctx([&](const GCtx& x, int64_t k) { GOrd::turn(x, a, k, gen); }),
+        with_ctx([&](const GCtx& x, int64_t r) -> int8_t {
+          SV w = x.v(s.o_w);
+          GOrd::close_row(x, a, r, w);
+          if (!(a.flags & SRNN_F_FUSED_CENSUS)) return -1;
+          return g_classify_w(x, w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, GItem::actx(a, s, (uint64_t)r, 0x7FFFFFF0u));
+        }));
     return 0;
-  }
-  if (!(a.flags & SRNN_F_TWO_PHASE) || !a.temp) {
-    set_error("device ordered soup generation: two-phase block stats (temp) needed");
-    return -5;
   }
   if (!a.scratch || a.scratch_bytes < gord_scratch_bytes(s, a.n)) {
     set_error("runtime-shape ordered generation: scratch missing or shorter than the run launch needs (one lane per "
               "turn plus the critical-list waves: srnn_generic_ord_scratch_bytes)");
     return -5;
   }
-  const int64_t nb = (a.n + TB - 1) / TB;
-  if (nb <= 0) return 0;
-  hipStream_t st = (hipStream_t)a.stream;
-  if (!planned) ord_plan_dev<GORD_RB, void>(c, a, false);
-  const SrnnArgs ra = ord_run_args(a, nb);
-  hipLaunchKernelGGL(k_gord_head, dim3(1), dim3(64), 0, st, s, a);
-  hipLaunchKernelGGL((k_ord_run<GOrdPol>), dim3((unsigned)ord_run_grid(ra, nb)), dim3(TB), 0, st, c, ra);
-  hipLaunchKernelGGL(k_gord_close, dim3((unsigned)nb), dim3(TB), 0, st, s, a);
-  if (!(a.flags & SRNN_F_GEN_COUNTS)) {
-    constexpr int FNT = SRNN_FINISH_NT;
-    hipLaunchKernelGGL((k_gen_finish<Weightwise<1, 1>, StF32, FNT>), dim3(1), dim3(FNT), 0, st, a, (int32_t)nb);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(hipGetErrorString(e));
-    return -3;
-  }
-  return 0;
+  return ord_generation_dev<GOrdPol>(c, s, a, 12, [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_gord_head, dim3(1), dim3(64), 0, st, s, a);
+  });
 }
 
 // lanes of a device launch and the scratch bytes they need
@@ -2638,7 +2516,7 @@ extern "C" int srnn_dispatch_generic(int op, const SrnnCfg* c, const SrnnArgs* a
       srnn::set_error(why);
       return -5;
     }
-    return op == OP_ORD_PLAN ? srnn::g_ord_plan(*c, *a) : srnn::g_soup_ordered(*c, s, *a);
+    return op == OP_ORD_PLAN ? srnn::ord_plan_op<srnn::GORD_RB, void>(*c, *a, true) : srnn::g_soup_ordered(*c, s, *a);
   }
   if (op == OP_GEN_FINISH) {  // shape independent: the batched / serial finish of srnn_kernels.h
     SrnnCfg dummy{};

@@ -43,6 +43,11 @@
 //                 generation as that attack's output), census class, the next generation's
 //                 decisions linked, block stats for the finish (newborn uids in slot order)
 //
+// k_ord_run and k_ord_close are templates over the net family's policy (OrdLanePol here,
+// BigOrdPol in srnn_bignet.h, GOrdPol in srnn_generic.hip: the turn, the final row and their
+// LDS); the argument checks, the host generation, the launch sequence and OP_ORD_PLAN
+// (ord_generation_args_ok / _host / _dev, ord_plan_op) are shared by every family.
+//
 // Every turn runs the serial loop's per-particle code with the same Philox streams (attack
 // keyed (k, gen*1024+1), SGD (k, gen*1024+512), newborn init respawn_key(gen, k)), and a
 // recomputed attack output is the same function of the same versions, so a generation
@@ -733,15 +738,19 @@ __device__ __forceinline__ int64_t ord_crit_at(const SrnnArgs& a, int64_t g, int
   return ord::run_order(a)[slot];
 }
 
-// every turn of the generation.  A lane first runs a turn without producers: turn k (or, with
-// the run order, the k-th of it: producers of later turns first, their waves at raised priority,
-// their permutations from the table).  Then the wave works in rounds: the records its lanes made
-// ready (each lane's list) are gathered into LDS and handed out one per lane -- a producer whose
-// row several turns read does not run those turns one after another -- each run as a
-// continuation (raised priority, permutations from the table) at level 1 + its deepest
-// producer's.  The wave ends when no lane has a ready record left.
-// (Pol: the turn of a net family and its LDS -- OrdLanePol below, the big aggregating nets'
-// in srnn_bignet.h; the schedule itself is shape independent)
+// the class counts of a wave's 64 rows (k: the lane's class, -1: none) into words 1..3 of their
+// block's stats `mine` (every lane of the wave calls it; word 0, the respawn ballot, is the close's)
+__device__ __forceinline__ void ord_bs_classes(unsigned long long* mine, int8_t k) {
+  uint32_t cnt[5];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) cnt[q] = (uint32_t)__popcll(__ballot(k == q));
+  if (threadIdx.x % TB == 0) {
+    mine[1] = (unsigned long long)cnt[0] | ((unsigned long long)cnt[1] << 32);
+    mine[2] = (unsigned long long)cnt[2] | ((unsigned long long)cnt[3] << 32);
+    mine[3] = (unsigned long long)cnt[4];
+  }
+}
+
 // the class counts of the 64-row block gb of final rows W into its block stats (words 1..3; the
 // close wrote the respawn ballot, word 0): the census of a close with SRNN_F_ORD_CENSUS_LATER, by
 // k_ord_census or by extra workgroups of the next generation's run launch (o_census_temp)
@@ -757,21 +766,13 @@ __device__ void ord_census_block(const SrnnCfg& c, const SrnnArgs& a, const floa
     I::load(I::rowp(W, r), w);
     k = I::classify_w(w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, I::actx(a, c, (uint64_t)r, 0x7FFFFFF0u, perm));
   }
-  uint32_t cnt[5];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) cnt[q] = (uint32_t)__popcll(__ballot(k == q));
-  if (lane == 0) {
-    uint64_t* mine = temp + gb * 4;
-    mine[1] = (uint64_t)cnt[0] | ((uint64_t)cnt[1] << 32);
-    mine[2] = (uint64_t)cnt[2] | ((uint64_t)cnt[3] << 32);
-    mine[3] = (uint64_t)cnt[4];
-  }
+  ord_bs_classes(reinterpret_cast<unsigned long long*>(temp) + gb * 4, k);
 }
 
 template <class Net, class S>
 struct OrdLanePol {
-  static constexpr bool SHADOW = true;
-  static constexpr bool CENSUS = true;  // extra run workgroups may take the previous close's census  // a turn is one lane's: idle lanes may repeat it (k_ord_run)
+  static constexpr bool SHADOW = true;  // a turn is one lane's: idle lanes may repeat it (k_ord_run)
+  static constexpr bool CENSUS = true;  // extra run workgroups may take the previous close's census
   static constexpr int SAMP = samp_slots<Net>();
   static constexpr int PERM = (Net::P + 4) & ~3;
   static constexpr int RB = ord::Ord<Net, S>::RB;  // the plan's recompute depth
@@ -788,7 +789,36 @@ struct OrdLanePol {
   __device__ static void census(const SrnnCfg& c, const SrnnArgs& a, int64_t gb, Shared& sh) {
     ord_census_block<Net, S>(c, a, a.W2, a.o_census_temp, gb, sh.perm + threadIdx.x * PERM);
   }
+  // the close (k_ord_close): row r's final version; its class, or -1 when the census is off or
+  // comes later (SRNN_F_ORD_CENSUS_LATER: k_ord_census, beside the next run -- nothing is loaded)
+  using CloseArg = SrnnCfg;
+  struct CloseShared {
+    uint8_t perm[TB * PERM];
+  };
+  // (forced inline: as a call of its own the row code of the wide nets is laid out differently --
+  // WW(8,2)'s close went from 432 to 1184 B of scratch per lane)
+  __device__ __forceinline__ static int8_t close(const SrnnCfg& c, const SrnnArgs& a, int64_t r, bool valid, int32_t gen,
+                                                 CloseShared& sh) {
+    using I = Item<Net, S>;
+    if (!valid) return -1;
+    uint8_t* perm = sh.perm + threadIdx.x * PERM;
+    float w[Net::P];
+    const bool later = (a.flags & SRNN_F_ORD_CENSUS_LATER) != 0;
+    if (later) ord::Ord<Net, S>::template close_row<false>(c, a, r, gen, perm, w);
+    else ord::Ord<Net, S>::close_row(c, a, r, gen, perm, w);
+    if (later || !(a.flags & SRNN_F_FUSED_CENSUS)) return -1;
+    return I::classify_w(w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, I::actx(a, c, (uint64_t)r, 0x7FFFFFF0u, perm));
+  }
 };
+// every turn of the generation.  A lane first runs a turn without producers: turn k (or, with
+// the run order, the k-th of it: producers of later turns first, their waves at raised priority,
+// their permutations from the table).  Then the wave works in rounds: the records its lanes made
+// ready (each lane's list) are gathered into LDS and handed out one per lane -- a producer whose
+// row several turns read does not run those turns one after another -- each run as a
+// continuation (raised priority, permutations from the table) at level 1 + its deepest
+// producer's.  The wave ends when no lane has a ready record left.
+// (Pol: the turn of a net family and its LDS -- OrdLanePol below, the big aggregating nets'
+// in srnn_bignet.h; the schedule itself is shape independent)
 template <class Pol>
 __global__ __launch_bounds__(TB) void k_ord_run(SrnnCfg c, SrnnArgs a) {
   __shared__ typename Pol::Shared s_sh;
@@ -1005,49 +1035,39 @@ __global__ __launch_bounds__(TB) void k_ord_run(SrnnCfg c, SrnnArgs a) {
 }
 
 // final rows, census, next decisions, block stats (the fused generation's two-phase form:
-// k_gen_finish / the batched finish number the newborns afterwards)
-template <class Net, class S>
-__global__ __launch_bounds__(TB) void k_ord_close(SrnnCfg c, SrnnArgs a) {
-  using I = Item<Net, S>;
-  constexpr int PERM = (Net::P + 4) & ~3;
-  __shared__ uint8_t s_perm[TB * PERM];
+// k_gen_finish / the batched finish number the newborns afterwards).  Pol, the run policy of the
+// net family, supplies the close's first argument (CloseArg), its LDS (CloseShared) and
+// close(arg, a, r, valid, gen, lds): row r's final version into W, its attack list consumed,
+// returning its census class or -1.  Every lane of the wave calls it (valid: r < n), so a close
+// may load its rows wave-cooperatively.
+template <class Pol>
+__global__ __launch_bounds__(TB) void k_ord_close(typename Pol::CloseArg c, SrnnArgs a) {
+  using Dec = typename ord::OrdSched<Pol::RB>::Dec;
+  __shared__ typename Pol::CloseShared s_sh;
   const int64_t gb = blockIdx.x;
   const int64_t r = gb * TB + threadIdx.x;
   const int lane = threadIdx.x;
-  uint8_t* perm = s_perm + lane * PERM;
-  const int32_t gen = I::gen_of(a);
-  const bool census = (a.flags & SRNN_F_FUSED_CENSUS) != 0;
+  const int32_t gen = Dec::gen_of(a);
   // (in-run planning: this set's barrier counter is free for the plan two generations on)
   if ((a.flags & SRNN_F_ORD_INPLAN) && gb == 0 && lane == 0) a.o_ctl[ord::BARW] = 0;
+  const bool valid = r < a.n;
+  if (valid && a.o_src[4 * r + 3] < 0) atomicOr(a.o_ctl + ord::ERRW, ord::ERR_NOT_RUN);  // never ran: a scheduling bug
+  const int8_t k = Pol::close(c, a, r, valid, gen, s_sh);
   bool rs = false;
-  int8_t k = -1;
-  const bool later = (a.flags & SRNN_F_ORD_CENSUS_LATER) != 0;  // the census: k_ord_census, beside the next run
-  if (r < a.n) {
-    if (a.o_src[4 * r + 3] < 0) atomicOr(a.o_ctl + ord::ERRW, ord::ERR_NOT_RUN);  // never ran: a scheduling bug
-    float w[Net::P];
-    if (later) ord::Ord<Net, S>::template close_row<false>(c, a, r, gen, perm, w);
-    else ord::Ord<Net, S>::close_row(c, a, r, gen, perm, w);
+  if (valid) {
     rs = a.respawn[r] != 0;
     if (!(a.flags & SRNN_F_ORD_PLANNED)) {  // (planned ahead: the next OP_ORD_PLAN links them)
       int64_t at, te;
-      I::decision(a, r, gen + 1, at, te);
-      if (at >= 0) I::link(a.heads_next, a.nexts_next, at, (uint32_t)r);
+      Dec::decision(a, r, gen + 1, at, te);
+      if (at >= 0) Dec::link(a.heads_next, a.nexts_next, at, (uint32_t)r);
     }
-    if (census && !later)
-      k = I::classify_w(w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, I::actx(a, c, (uint64_t)r, 0x7FFFFFF0u, perm));
   }
-  if ((a.flags & SRNN_F_GEN_COUNTS) && gb == 0 && lane == 0) I::set_gen(a, gen + 1);
+  if ((a.flags & SRNN_F_GEN_COUNTS) && gb == 0 && lane == 0) Dec::set_gen(a, gen + 1);
   const unsigned long long m = __ballot(rs);
-  uint32_t cnt[5];
-#pragma unroll
-  for (int q = 0; q < 5; ++q) cnt[q] = (uint32_t)__popcll(__ballot(k == q));
+  unsigned long long* bs = reinterpret_cast<unsigned long long*>(a.temp);
+  ord_bs_classes(bs + gb * 4, k);
   if (lane == 0) {
-    unsigned long long* bs = reinterpret_cast<unsigned long long*>(a.temp);
-    unsigned long long* mine = bs + gb * 4;
-    mine[0] = m;
-    mine[1] = (unsigned long long)cnt[0] | ((unsigned long long)cnt[1] << 32);
-    mine[2] = (unsigned long long)cnt[2] | ((unsigned long long)cnt[3] << 32);
-    mine[3] = (unsigned long long)cnt[4];
+    bs[gb * 4] = m;
     if ((a.flags & SRNN_F_BORN_TOTAL) && m) atomicAdd(bs + ((a.n + TB - 1) / TB) * 4, (unsigned long long)__popcll(m));
   }
   // SRNN_F_ORD_SYNC: the launch ends (and the next run starts) once the next generation's plan is done
@@ -1140,7 +1160,8 @@ inline SrnnArgs ord_next_plan_args(const SrnnArgs& a) {
   return pa;
 }
 
-inline SrnnArgs ord_run_args(const SrnnArgs& a, int64_t nb) {
+// (bulk_delay: the family's default head start of the critical roots, us)
+inline SrnnArgs ord_run_args(const SrnnArgs& a, int64_t nb, int bulk_delay = 12) {
   SrnnArgs ra = a;
   // (defaults measured, profiles/r6a r6q-r6r: per-wave lists 0.173 ms vs the ready queue 0.296; shadow
   // lanes in rounds of <= 32 turns 0.160-0.162, <= 16 0.161-0.162, <= 63 0.163-0.165, off 0.172-0.173)
@@ -1149,7 +1170,7 @@ inline SrnnArgs ord_run_args(const SrnnArgs& a, int64_t nb) {
   // (the turn waves start 12 us after the critical-list waves: the roots' SGD chains run their first
   // epochs before the bulk pulls the clock down; measured 0: 0.163-0.164 ms, 6: 0.160-0.162, 10:
   // 0.158-0.161, 14: 0.159-0.160, 20: 0.159-0.160, 35: 0.164, profiles/r6a r6i-r6j)
-  ra.o_bulk_delay = std::min(1000, std::max(0, knob(SRNN_KNOB_ORD_BULK_DELAY, 12)));
+  ra.o_bulk_delay = std::min(1000, std::max(0, knob(SRNN_KNOB_ORD_BULK_DELAY, bulk_delay)));
   if (knob(SRNN_KNOB_ORD_CRIT, 1) != 0) {
     ra.flags |= SRNN_F_ORD_CRIT;
     ra.x_groups = (int32_t)std::min<int64_t>(nb, (ord::rec_total(a.n) + TB - 1) / TB);
@@ -1224,10 +1245,10 @@ inline bool ord_single_table(const SrnnArgs& a) {
   return true;
 }
 
-// OP_ORD_PLAN of a lane-template net (the big aggregating nets: srnn_bignet.h)
-template <class Net, class S>
-int soup_ord_plan(const SrnnCfg& c, const SrnnArgs& a) {
-  constexpr int RB = ord::Ord<Net, S>::RB;
+// OP_ORD_PLAN of every net family (the schedule is shape independent: RB the family's recompute
+// depth, PT its permutation-table net or void; host_allowed: the family has a host form)
+template <int RB, class PT>
+int ord_plan_op(const SrnnCfg& c, const SrnnArgs& a, bool host_allowed) {
   if (!ord_single_table(a)) return -5;
   if (!a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts) {
     set_error("ordered generation plan needs o_src, o_list, o_ctl and the planned generation's (NIL) attack lists");
@@ -1238,10 +1259,13 @@ int soup_ord_plan(const SrnnCfg& c, const SrnnArgs& a) {
     return -5;
   }
   if (!a.dev) {
+    if (!host_allowed) {
+      set_error("ordered generation plan: this net family runs on the GPU only");
+      return -5;
+    }
     ord_plan_host<RB>(a, true);
     return 0;
   }
-  using PT = std::conditional_t<(Net::KIND == 0 && Net::P <= 16), Net, void>;
   ord_plan_dev<RB, PT>(c, a, true);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -1260,74 +1284,79 @@ int soup_ord_plan(const SrnnCfg& c, const SrnnArgs& a) {
 // next generation's (linked here, unless SRNN_F_ORD_PLANNED: the plan was built ahead by
 // OP_ORD_PLAN, which links its own lists).  Device: the block stats of the two-phase fused
 // generation in temp (SRNN_F_TWO_PHASE); host: the finish inline (uids, census, counter).
-template <class Net, class S>
-int soup_ordered(const SrnnCfg& c, const SrnnArgs& a) {
-  using I = Item<Net, S>;
-  using O = ord::Ord<Net, S>;
+// The net families (soup_ordered below, big_soup_ordered, g_soup_ordered) share the argument
+// checks, the host generation and the device launch sequence that follow.
+inline bool ord_generation_args_ok(const SrnnArgs& a, bool host_allowed) {
   const bool planned = (a.flags & SRNN_F_ORD_PLANNED) != 0;
-  if (!ord_single_table(a)) return -5;
+  if (!ord_single_table(a)) return false;
+  // (o_levels bounds the host path's passes: a family without a host form does not read it)
   if (!a.W || !a.W2 || !a.W3 || !a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts ||
-      (!planned && (!a.heads_next || !a.nexts_next)) || !a.respawn || a.o_levels < 1 ||
-      a.o_levels > ord::MAX_LEVELS) {
+      (!planned && (!a.heads_next || !a.nexts_next)) || !a.respawn ||
+      (host_allowed && (a.o_levels < 1 || a.o_levels > ord::MAX_LEVELS))) {
     set_error("ordered soup generation needs W, W2, W3, o_src, o_list, o_ctl, the attack lists (both unless "
               "planned ahead), respawn and 1 <= o_levels <= 16");
-    return -5;
+    return false;
   }
-  if (!ord_inplan_ok(a) || !ord_sync_ok(a) || !ord_census_later_ok(a)) return -5;
-  if (!a.dev) {
-    const int32_t gen = I::gen_of(a);
-    if (!planned) ord_plan_host<O::RB>(a, false);
-    // levels in index order (every producer precedes its consumer)
-    std::vector<std::vector<int64_t>> lists;
-    for (int64_t k = 0; k < a.n; ++k) {
-      const int32_t lv = a.o_src[4 * k + 3];
-      if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
-      lists[(size_t)lv].push_back(k);
-    }
-    for (const auto& li : lists)
-      host_parallel((int64_t)li.size(), [&](int64_t q) {
-        float4 samp[Net::P + 1];
-        uint8_t perm[Net::P + 4];
-        O::turn(c, a, li[(size_t)q], gen, samp, perm);
-      });
-    std::vector<int8_t> ks((size_t)a.n, (int8_t)-1);
-    const bool census = (a.flags & SRNN_F_FUSED_CENSUS) != 0;
-    host_parallel(a.n, [&](int64_t r) {
-      float w[Net::P];
-      uint8_t perm[Net::P + 4];
-      O::close_row(c, a, r, gen, perm, w);
-      if (census)
-        ks[(size_t)r] = I::classify_w(w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0,
-                                      I::actx(a, c, (uint64_t)r, 0x7FFFFFF0u, perm));
-    });
-    if (!planned)
-      for (int64_t r = 0; r < a.n; ++r) {
-        int64_t at, te;
-        I::decision(a, r, gen + 1, at, te);
-        if (at >= 0) {
-          a.nexts_next[r] = a.heads_next[at];
-          a.heads_next[at] = (uint32_t)r;
-        }
-      }
-    uint64_t cs[5] = {0, 0, 0, 0, 0};
-    for (int64_t r = 0; r < a.n; ++r)
-      if (ks[(size_t)r] >= 0) cs[ks[(size_t)r]]++;
-    int64_t u = a.uid_base ? a.uid_base[0] : 0, total = 0;
-    for (int64_t r = 0; r < a.n; ++r)
-      if (a.respawn[r]) {
-        if (a.uid_out) a.uid_out[r] = u;
-        ++u;
-        ++total;
-      }
-    if (a.uid_base) a.uid_base[0] = u;
-    I::set_gen(a, gen + 1);
-    if (a.counts) {
-      for (int q = 0; q < 5; ++q) a.counts[q] = census ? cs[q] : 0;
-      a.counts[5] = (uint64_t)total;
-    }
-    if (a.flags & SRNN_F_ORD_INPLAN) ord_plan_host<O::RB>(ord_next_plan_args(a), true);  // the next plan
-    return 0;
+  if (!a.dev && !host_allowed) {
+    set_error("ordered soup generation: this net family runs on the GPU only");
+    return false;
   }
+  return ord_inplan_ok(a) && ord_sync_ok(a) && ord_census_later_ok(a);
+}
+
+// host: the generation level by level (every producer precedes its consumer), the rows closed,
+// the next decisions linked, the finish inline (census, uids in slot order, counter) and, with
+// SRNN_F_ORD_INPLAN, the next plan.  turn(k) runs turn k; close_class(r) leaves row r's final
+// version in W and returns its census class or -1; both are called from the host thread pool.
+template <int RB, class Turn, class Close>
+void ord_generation_host(const SrnnArgs& a, Turn&& turn, Close&& close_class) {
+  using Dec = typename ord::OrdSched<RB>::Dec;
+  const bool planned = (a.flags & SRNN_F_ORD_PLANNED) != 0;
+  const int32_t gen = Dec::gen_of(a);
+  if (!planned) ord_plan_host<RB>(a, false);
+  std::vector<std::vector<int64_t>> lists;
+  for (int64_t k = 0; k < a.n; ++k) {
+    const int32_t lv = a.o_src[4 * k + 3];
+    if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
+    lists[(size_t)lv].push_back(k);
+  }
+  for (const auto& li : lists) host_parallel((int64_t)li.size(), [&](int64_t q) { turn(li[(size_t)q]); });
+  std::vector<int8_t> ks((size_t)a.n, (int8_t)-1);
+  host_parallel(a.n, [&](int64_t r) { ks[(size_t)r] = close_class(r); });
+  if (!planned)
+    for (int64_t r = 0; r < a.n; ++r) {
+      int64_t at, te;
+      Dec::decision(a, r, gen + 1, at, te);
+      if (at >= 0) {
+        a.nexts_next[r] = a.heads_next[at];
+        a.heads_next[at] = (uint32_t)r;
+      }
+    }
+  uint64_t cs[5] = {0, 0, 0, 0, 0};
+  for (int64_t r = 0; r < a.n; ++r)
+    if (ks[(size_t)r] >= 0) cs[ks[(size_t)r]]++;
+  int64_t u = a.uid_base ? a.uid_base[0] : 0, total = 0;
+  for (int64_t r = 0; r < a.n; ++r)
+    if (a.respawn[r]) {
+      if (a.uid_out) a.uid_out[r] = u;
+      ++u;
+      ++total;
+    }
+  if (a.uid_base) a.uid_base[0] = u;
+  Dec::set_gen(a, gen + 1);
+  if (a.counts) {
+    for (int q = 0; q < 5; ++q) a.counts[q] = cs[q];
+    a.counts[5] = (uint64_t)total;
+  }
+  if (a.flags & SRNN_F_ORD_INPLAN) ord_plan_host<RB>(ord_next_plan_args(a), true);  // the next plan
+}
+
+// device: [plan ->] run -> close [-> finish, unless the caller batches it] of the family Pol (its
+// run policy: turn and close; ca: the close's first argument).  bulk_delay: ord_run_args;
+// before_run(stream): the family's own launch ahead of the run, if any.
+template <class Pol, class BeforeRun>
+int ord_generation_dev(const SrnnCfg& c, const typename Pol::CloseArg& ca, const SrnnArgs& a, int bulk_delay,
+                       BeforeRun&& before_run) {
   if (!(a.flags & SRNN_F_TWO_PHASE) || !a.temp) {
     set_error("device ordered soup generation: two-phase block stats (temp) needed");
     return -5;
@@ -1335,14 +1364,14 @@ int soup_ordered(const SrnnCfg& c, const SrnnArgs& a) {
   const int64_t nb = (a.n + TB - 1) / TB;
   if (nb <= 0) return 0;
   hipStream_t st = (hipStream_t)a.stream;
-  using PT = std::conditional_t<(Net::KIND == 0 && Net::P <= 16), Net, void>;
-  if (!planned) ord_plan_dev<O::RB, PT>(c, a, false);
-  const SrnnArgs ra = ord_run_args(a, nb);
-  hipLaunchKernelGGL((k_ord_run<OrdLanePol<Net, S>>), dim3((unsigned)ord_run_grid(ra, nb)), dim3(TB), 0, st, c, ra);
-  hipLaunchKernelGGL((k_ord_close<Net, S>), dim3((unsigned)nb), dim3(TB), 0, st, c, a);
-  if (!(a.flags & SRNN_F_GEN_COUNTS)) {
+  if (!(a.flags & SRNN_F_ORD_PLANNED)) ord_plan_dev<Pol::RB, typename Pol::PT>(c, a, false);
+  const SrnnArgs ra = ord_run_args(a, nb, bulk_delay);
+  before_run(st);
+  hipLaunchKernelGGL((k_ord_run<Pol>), dim3((unsigned)ord_run_grid(ra, nb)), dim3(TB), 0, st, c, ra);
+  hipLaunchKernelGGL((k_ord_close<Pol>), dim3((unsigned)nb), dim3(TB), 0, st, ca, a);
+  if (!(a.flags & SRNN_F_GEN_COUNTS)) {  // (the finish reads the net only for the generation counter)
     constexpr int FNT = SRNN_FINISH_NT;
-    hipLaunchKernelGGL((k_gen_finish<Net, S, FNT>), dim3(1), dim3(FNT), 0, st, a, (int32_t)nb);
+    hipLaunchKernelGGL((k_gen_finish<Weightwise<1, 1>, StF32, FNT>), dim3(1), dim3(FNT), 0, st, a, (int32_t)nb);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -1350,6 +1379,33 @@ int soup_ordered(const SrnnCfg& c, const SrnnArgs& a) {
     return -3;
   }
   return 0;
+}
+
+// OP_SOUP_ORDERED of a lane-template net
+template <class Net, class S>
+int soup_ordered(const SrnnCfg& c, const SrnnArgs& a) {
+  using I = Item<Net, S>;
+  using O = ord::Ord<Net, S>;
+  if (!ord_generation_args_ok(a, true)) return -5;
+  if (!a.dev) {
+    const int32_t gen = I::gen_of(a);
+    ord_generation_host<O::RB>(
+        a,
+        [&](int64_t k) {
+          float4 samp[Net::P + 1];
+          uint8_t perm[Net::P + 4];
+          O::turn(c, a, k, gen, samp, perm);
+        },
+        [&](int64_t r) -> int8_t {
+          float w[Net::P];
+          uint8_t perm[Net::P + 4];
+          O::close_row(c, a, r, gen, perm, w);
+          if (!(a.flags & SRNN_F_FUSED_CENSUS)) return -1;
+          return I::classify_w(w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, I::actx(a, c, (uint64_t)r, 0x7FFFFFF0u, perm));
+        });
+    return 0;
+  }
+  return ord_generation_dev<OrdLanePol<Net, S>>(c, c, a, 12, [](hipStream_t) {});
 }
 
 #include "srnn_ordered_sh.h"

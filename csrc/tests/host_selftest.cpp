@@ -393,6 +393,11 @@ int main() {
   ordered_soup(ww22(), 257, 4, 1);
   ordered_soup(ww22(), 257, 4, 2);
   ordered_soup(agg422(), 129, 3, 2);
+  // runtime shapes: the shared host generation's second caller (srnn_generic.hip)
+  ordered_soup(cfg(0, 3, 3, 0, 33), 129, 3, 0);     // Weightwise(3,3)
+  ordered_soup(cfg(0, 3, 3, 0, 33), 129, 3, 2);
+  ordered_soup(cfg(2, 3, 2, 0, 34), 129, 3, 0);     // Recurrent(3,2)
+  ordered_soup(cfg(2, 3, 2, 0, 34), 129, 3, 2);
   seq_soup(ww22(), 257, 4);
   seq_soup(agg422(), 129, 3);
   ops_smoke(ww22(), 1000);

@@ -1,5 +1,5 @@
 """Reference-order soups of runtime shapes on the device (csrc/srnn_generic.hip: GOrd, GOrdPol in
-k_ord_run, k_gord_close):
+k_ord_run and k_ord_close):
 
 A. the template shapes forced onto the runtime-shape path == the template engine on the same device,
    bitwise, eager and graph-captured (the template side is proven bitwise the serial loop);

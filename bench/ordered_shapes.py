@@ -1,9 +1,11 @@
 """Reference-order soups of runtime shapes on the device: ms per generation.
 
-For WW(3,3), WW(10,3), Agg(4,4,3) and RNN(8,2) at the bench parameters (attack 0.1, learn 0.1,
+For WW(3,3), WW(10,3), WW(16,2), Agg(4,4,3) and RNN(8,2) at the bench parameters (attack 0.1, learn 0.1,
 train 20, respawn) this times one generation of ``SoupEngine(order="sequential")`` -- the
 continuation-scheduled generation with the runtime-shape turn (csrc/srnn_generic.hip GOrd) --
-eagerly and replayed from hipGraphs, and reports its dependency levels.  Beside it: the
+eagerly and replayed from hipGraphs, and reports its dependency levels and run form (``--ord-wave
+0``: the wide Weightwise shapes' turns on one lane each instead of a group of lanes, the library
+knob SRNN_ORD_WAVE).  Beside it: the
 synchronous (Jacobi) soup of the same shape with the wave kernels on and off, and the host serial
 loop (``SequentialSoupEngine``) at 2,000 particles scaled per particle.
 
@@ -11,7 +13,7 @@ The driver runs every step in a child process of its own under a time limit and 
 first step that fails; each step prints one JSON line.  ``--markdown`` adds the table of
 profiles/ordered_runtime_shapes.md.
 
-    python bench/ordered_shapes.py [--n 100000] [--gens 3] [--shapes ww33,ww103,agg443,rnn82]
+    python bench/ordered_shapes.py [--n 100000] [--gens 3] [--shapes ww33,ww103,ww162,agg443,rnn82] [--ord-wave 0|1]
 """
 from __future__ import annotations
 
@@ -27,7 +29,8 @@ sys.path.insert(0, ROOT)
 
 PARAMS = dict(attacking_rate=0.1, learn_from_rate=0.1, train=20, learn_from_severity=1, remove_divergent=True,
               remove_zero=True, epsilon=1e-4)
-SHAPES = {"ww33": ("weightwise", (3, 3)), "ww103": ("weightwise", (10, 3)), "agg443": ("aggregating", (4, 4, 3)),
+SHAPES = {"ww33": ("weightwise", (3, 3)), "ww103": ("weightwise", (10, 3)), "ww162": ("weightwise", (16, 2)),
+          "agg443": ("aggregating", (4, 4, 3)),
           "rnn82": ("recurrent", (8, 2))}
 STEPS = ("ordered-eager", "ordered-graph", "sync-waves", "sync-lanes", "host-serial")
 
@@ -47,7 +50,7 @@ def _timed(engine, gens):
     return (time.perf_counter() - t) / gens * 1e3
 
 
-def step(name, shape, n, gens, host_n):
+def step(name, shape, n, gens, host_n, ord_wave=None):
     import torch
     from self_replicating_neural_networks_amd.config import ExecConfig
     from self_replicating_neural_networks_amd.seq_soup import SequentialSoupEngine
@@ -67,7 +70,8 @@ def step(name, shape, n, gens, host_n):
     if not torch.cuda.is_available():
         raise SystemExit("ordered_shapes: no GPU (a measurement does not fall back to the host)")
     if name.startswith("ordered"):
-        ex = ExecConfig(graph_chunks=(2,))
+        ex = ExecConfig(graph_chunks=(2,), ord_wave=ord_wave)
+        ex.apply_library()
         e = SoupEngine(spec, n, PARAMS, device="cuda", seed=1, order="sequential", execution=ex)
         assert e._ord_generic, "not a runtime shape"
         if name == "ordered-graph":
@@ -77,7 +81,7 @@ def step(name, shape, n, gens, host_n):
         lv = e.ordered_levels()
         assert lv["error"] == 0, lv
         out.update(n=n, ms_per_gen=round(ms, 3), levels=lv["levels"], tail=lv["tail"], max_level=lv["max_level"],
-                   pending=lv["pending"], stored_attacks=lv["stored_attacks"],
+                   pending=lv["pending"], run_form=e.ordered_run_form(), stored_attacks=lv["stored_attacks"],
                    scratch_mb=round(e._scratch.numel() / 2 ** 20, 1), census=e.count())
         e.release_graphs()
         return out
@@ -117,17 +121,23 @@ def main():
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--steps", default=",".join(STEPS))
     ap.add_argument("--step-timeout", type=int, default=150)
+    ap.add_argument("--ord-wave", type=int, choices=(0, 1), default=None,
+                    help="reference-order turns of the wide Weightwise shapes on lane groups (1) or lanes (0); "
+                         "default: the library's choice")
     ap.add_argument("--markdown", action="store_true")
     ap.add_argument("--child", nargs=2, metavar=("STEP", "SHAPE"))
     args = ap.parse_args()
     if args.child:
-        print(json.dumps(step(args.child[0], args.child[1], args.n, args.gens, args.host_n)), flush=True)
+        ow = None if args.ord_wave is None else bool(args.ord_wave)
+        print(json.dumps(step(args.child[0], args.child[1], args.n, args.gens, args.host_n, ow)), flush=True)
         return 0
     rows = []
     for shape in args.shapes.split(","):
         for name in args.steps.split(","):
             cmd = [sys.executable, os.path.abspath(__file__), "--n", str(args.n), "--gens", str(args.gens), "--host-n",
                    str(args.host_n), "--child", name, shape]
+            if args.ord_wave is not None:
+                cmd += ["--ord-wave", str(args.ord_wave)]
             try:
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout, cwd=ROOT)
             except subprocess.TimeoutExpired:

@@ -263,7 +263,7 @@ enum SrnnOp {
                         // independent: issued on a side stream while the previous generation runs
 };
 
-int srnn_abi_version();  // 31
+int srnn_abi_version();  // 32
 int64_t srnn_args_size();  // sizeof(SrnnArgs): the ctypes mirror checks its layout against it
 int64_t srnn_cfg_size();
 int srnn_has_config(const SrnnCfg* cfg);
@@ -294,7 +294,9 @@ enum SrnnKnob {
                                 //   turn; 0: off; default 32)
   SRNN_KNOB_ORD_BULK_DELAY = 11, // SRNN_ORD_BULK_DELAY: microseconds a reference-order run's turn waves (not the
                                  //   critical-list waves) wait before their first turn (default 12)
-  SRNN_KNOB_COUNT = 12
+  SRNN_KNOB_ORD_WAVE = 12,      // SRNN_ORD_WAVE: reference-order turns of the wide Weightwise runtime shapes on a
+                                //   group of lanes each (1, default) or one lane each (0)
+  SRNN_KNOB_COUNT = 13
 };
 void srnn_set_knob(int knob, int value);
 int srnn_get_knob(int knob);
@@ -308,6 +310,10 @@ int64_t srnn_generic_scratch_bytes(const SrnnCfg* cfg, int64_t n, int64_t max_la
 int64_t srnn_ord_run_lanes(int64_t n);
 int64_t srnn_generic_ord_scratch_bytes(const SrnnCfg* cfg, int64_t n);
 int srnn_generic_supports(const SrnnCfg* cfg, int op, int dev);
+// the run form of a reference-order generation of this configuration on the host (dev 0) / device
+// (dev 1), the knobs in force counted: 0 none, 1 a lane per turn, 2 a group of lanes per turn
+int srnn_ord_run_form(const SrnnCfg* cfg, int dev);
+int srnn_generic_ord_run_form(const SrnnCfg* cfg, int dev);
 // temp bytes of a chunk-state run_fixpoint (big aggregating nets) over n rows: state float[n][aggregates] +
 // flags int8[n]; dense != 0: + (16-byte aligned) the chunk-state trajectory float[steps][n][aggregates]
 // that a dense recording is expanded from

@@ -116,10 +116,11 @@ namespace {
 const char* const g_knob_env[SRNN_KNOB_COUNT] = {"SRNN_FORCE_GENERIC", "SRNN_RNN_WAVE", "SRNN_RNN_SPEC",
                                                  "SRNN_RNN_SOUP",      "SRNN_WW_WAVE",  "SRNN_BIG_WAVE",
                                                  "SRNN_FIX_GROUP",     "SRNN_SOUP_LANES", "SRNN_ORD_CRIT",
-                                                 "SRNN_ORD_QUEUE",     "SRNN_ORD_SHADOW", "SRNN_ORD_BULK_DELAY"};
+                                                 "SRNN_ORD_QUEUE",     "SRNN_ORD_SHADOW", "SRNN_ORD_BULK_DELAY",
+                                                 "SRNN_ORD_WAVE"};
 // (every knob starts at -1 = its built-in default)
-int g_knob[SRNN_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-static_assert(sizeof(g_knob) / sizeof(g_knob[0]) == SRNN_KNOB_COUNT && SRNN_KNOB_COUNT == 12, "one -1 per knob");
+int g_knob[SRNN_KNOB_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+static_assert(sizeof(g_knob) / sizeof(g_knob[0]) == SRNN_KNOB_COUNT && SRNN_KNOB_COUNT == 13, "one -1 per knob");
 }  // namespace
 namespace srnn {
 int knob(int id, int dflt) {
@@ -234,7 +235,7 @@ __global__ void k_stream_probe_set(int32_t* f) {
 
 extern "C" {
 
-int srnn_abi_version() { return 31; }
+int srnn_abi_version() { return 32; }
 
 int srnn_stream_probe(int32_t* flag, void* side, void* main_stream, int64_t timeout_us) {
   hipLaunchKernelGGL(k_stream_probe_wait, dim3(1), dim3(64), 0, (hipStream_t)side, flag, timeout_us * 100);
@@ -279,6 +280,17 @@ int srnn_supports(const SrnnCfg* cfg, int op, int dev) {
   const int r = route(op, cfg, &probe);
   if (r == 0) return 1;
   return r == 1 && srnn_generic_supports(cfg, op, dev) ? 1 : 0;
+}
+
+// the run form that serves a reference-order generation of this configuration on the host (dev 0)
+// / device (dev 1), the knobs in force counted: 0 none, 1 a lane per turn (k_ord_run), 2 a group of
+// lanes per turn (the wide Weightwise runtime shapes, srnn_generic.hip)
+int srnn_ord_run_form(const SrnnCfg* cfg, int dev) {
+  SrnnArgs probe{};
+  probe.dev = dev;
+  const int r = route(OP_SOUP_ORDERED, cfg, &probe);
+  if (r == 0) return 1;
+  return r == 1 ? srnn_generic_ord_run_form(cfg, dev) : 0;
 }
 
 int srnn_run(int op, const SrnnCfg* cfg, const SrnnArgs* a) {

@@ -2360,6 +2360,305 @@ __global__ void k_gord_head(GShape s, SrnnArgs a) {
   for (int i = threadIdx.x; i < (int)(sizeof(GShape) / 4); i += blockDim.x) d[i] = src[i];
 }
 
+// ----------------------------------------------------------------------------------------------
+// The group run of the wide Weightwise nets (k_gord_run_ww): a reference-order turn on the U lanes
+// per particle of the WWave kernels instead of one lane of the engine above, whose every weight,
+// activation and sample goes through the element-major scratch in HBM.  One wave per workgroup
+// holds G = 64 / U turns at a time; lane u of a group computes unit u (ww_epochs_any), the own row
+// sits in the group's padded LDS weights, the coordinate table in LDS once per workgroup.  The turn
+// is GOrd::turn step for step (recompute depth 0), so a generation is bitwise the lane run's.
+//
+// The schedule is k_ord_run's per-wave lists over the same plan, records and consumer lists: a wave
+// first takes the G turns of its index positions that have no producer (every root exactly once:
+// the critical list is not used, a launch without SRNN_F_ORD_CRIT), then works in rounds -- each
+// group's leader lane publishes its turn (ord::publish: the rows drained and released at agent
+// scope before the counts go down), the wave gathers the records its leaders made ready, hands one
+// to each group and runs them at level 1 + the deepest producer's.  No wave waits for another.  No
+// ready queue, shadow lanes, bulk delay, census workgroups or in-run plan: the knobs of those are
+// not read here, and a generation that asks for an in-run plan stays on the lane run.
+//
+// LDS of a group: the WWave training regions, then the attack output (P), the victim row (P) and
+// the per-lane forward vectors (2 U W); after the groups the wave's G handed-out records.
+static bool ww_ord_geom(const GShape& s, WWave& g) {
+  if (!ww_wave_geom(s, g)) return false;
+  g.GS = g.o_misc + 4 + 2 * s.P + 2 * g.U * s.W;
+  return true;
+}
+static size_t ww_ord_lds(const GShape& s, const WWave& g) {
+  return ((size_t)3 * s.P + (size_t)g.G * g.GS + 64) * 4;
+}
+
+// the stored row of version `code` (GOrd::read_version: a code that names no row reads nothing
+// and sets ERR_SYNC)
+__device__ __forceinline__ const char* gw_version(const GShape& s, const SrnnArgs& a, int32_t code) {
+  const int64_t j = code >= 0 ? (int64_t)(code >> 1) : -(int64_t)code - 1;
+  if (j >= a.n) {
+    atomicOr(a.o_ctl + ord::ERRW, ord::ERR_SYNC);
+    return nullptr;
+  }
+  if (code < 0) return GItem::rowp(s, a.W2, j);
+  return (code & 1) ? GItem::rowp(s, a.W, j) : GItem::rowp(s, a.W3, j);
+}
+__device__ __forceinline__ void gw_store_flat(const GShape& s, const WWave& g, const float* v, char* row, int u) {
+  for (int k = u; k < s.PP; k += g.U) {
+    const float x = k < s.P ? v[k] : 0.f;
+    if (s.dtype == 0) reinterpret_cast<float*>(row)[k] = x;
+    else reinterpret_cast<uint16_t*>(row)[k] = s.dtype == 1 ? StBF16::enc(x) : StF16::enc(x);
+  }
+}
+
+// turn k of the lane's group (k < 0: the group sits this round out -- it goes through every epoch
+// call and barrier with its writes masked).  gm: the ballot mask of the group's lanes.
+template <int WT, int DT>
+__device__ __forceinline__ void gord_ww_turn(const GShape& s, const WWave& g, const SrnnArgs& a, const WWGroup& R,
+                                             const float* coords, int u, unsigned long long gm, int64_t k, int32_t gen,
+                                             bool shuffle, const Rng& rng) {
+  const int W = s.W, D = s.D, P = s.P;
+  const bool active = k >= 0;
+  float* ob = R.ob;       // A(k), flat
+  float* vb = R.ob + P;   // the victim's row, flat
+  float* h = vb + P + u * 2 * W;
+  float* h2 = h + W;
+  int64_t at = -1, te = -1;
+  int32_t sc[3] = {ord::SRC_NONE, ord::SRC_NONE, ord::SRC_NONE};
+  if (active) {
+    GOrd::Dec::decision(a, k, gen, at, te);
+    const int32_t* p = a.o_src + 4 * k;
+    sc[0] = p[0], sc[1] = p[1], sc[2] = p[2];
+    const char* r = gw_version(s, a, sc[0]);
+    if (r) ww_load(s, g, R.w, r, u);
+  }
+  int8_t act = A_NONE;
+  int64_t cp = -1;
+  // 1. attack: A(k) = f_k(victim) -- the own net (a flat copy in sv) at the victim's P weight
+  // points, the lanes of the group over the points
+  const bool atk = active && at >= 0;
+  const bool doA = atk && ord::needs_A(a, k, sc);
+  __syncthreads();
+  if (__ballot(doA) != 0ull) {
+    if (doA) {
+      for (int q = u; q < P; q += g.U) R.sv[q] = R.w[ww_pidx(s, g, q)];
+      const char* r = at == k ? nullptr : gw_version(s, a, sc[1]);
+      if (at == k) {
+        for (int q = u; q < P; q += g.U) vb[q] = R.w[ww_pidx(s, g, q)];
+      } else if (r) {
+        for (int q = u; q < P; q += g.U) vb[q] = g_dec(r, q, s.dtype);
+      }
+    }
+    __syncthreads();
+    if (doA) {
+      for (int q = u; q < P; q += g.U) {
+        const float x0 = vb[q], x1 = coords[3 * q], x2 = coords[3 * q + 1], x3 = coords[3 * q + 2];
+        const float* K = R.sv;  // flat: layer l at s.off[l], row-major (rows x cols)
+        for (int c = 0; c < W; ++c) {
+          float acc = x0 * K[c];
+          acc = fmaf(x1, K[W + c], acc);
+          acc = fmaf(x2, K[2 * W + c], acc);
+          acc = fmaf(x3, K[3 * W + c], acc);
+          h[c] = acc;
+        }
+        for (int l = 1; l < D; ++l) {
+          const float* Kl = R.sv + s.off[l];
+          for (int c = 0; c < W; ++c) {
+            float acc = h[0] * Kl[c];
+            for (int r = 1; r < W; ++r) acc = fmaf(h[r], Kl[r * W + c], acc);
+            h2[c] = acc;
+          }
+          for (int c = 0; c < W; ++c) h[c] = h2[c];
+        }
+        const float* KD = R.sv + s.off[D];
+        float y = h[0] * KD[0];
+        for (int r = 1; r < W; ++r) y = fmaf(h[r], KD[r], y);
+        ob[q] = g_q(y, s.dtype);
+      }
+    }
+    __syncthreads();
+    if (doA) {
+      if (ord::stored(a, k)) gw_store_flat(s, g, ob, GItem::rowp(s, a.W3, k), u);
+      if (at == k)
+        for (int q = u; q < P; q += g.U) R.w[ww_pidx(s, g, q)] = ob[q];
+    }
+    __syncthreads();
+  }
+  if (atk) act = A_ATTACKING, cp = at;
+  // 2. learn_from the teacher's current row (its own row, its attack output or a version)
+  const bool learn = active && te >= 0;
+  if (learn) {
+    if (sc[2] == ord::SRC_SELF) {
+      for (int q = u; q < P; q += g.U) R.sv[q] = R.w[ww_pidx(s, g, q)];
+    } else if (sc[2] == ord::SRC_ATK) {
+      for (int q = u; q < P; q += g.U) R.sv[q] = ob[q];
+    } else if (const char* r = gw_version(s, a, sc[2])) {
+      for (int q = u; q < P; q += g.U) R.sv[q] = g_dec(r, q, s.dtype);
+    }
+  }
+  __syncthreads();
+  const uint32_t c0 = (uint32_t)gen * 1024u + 512u;
+  const uint64_t uid = active ? (uint64_t)k : 0;
+  float loss = 0.f;
+  if (__ballot(learn) != 0ull && a.severity > 0) {
+    uint32_t ctr = c0;
+    const float l2 = ww_epochs_any<WT, DT>(s, g, R, coords, u, learn, a.severity, false, uid, ctr, a.lr, shuffle, rng);
+    if (learn) loss = l2;
+  }
+  if (learn) act = A_LEARN_FROM, cp = te;
+  if (a.epochs > 0) {  // 3. self-train
+    uint32_t ctr = c0 + ((learn && a.severity > 0) ? (uint32_t)a.severity : 0u);
+    loss = ww_epochs_any<WT, DT>(s, g, R, coords, u, active, a.epochs, true, uid, ctr, a.lr, shuffle, rng);
+    act = A_TRAIN_SELF;
+    cp = -1;
+  }
+  // 4. respawn (the stored state decides)
+  bool bad = false, nz = false;
+  if (active)
+    for (int q = u; q < P; q += g.U) {
+      float& v = R.w[ww_pidx(s, g, q)];
+      v = g_q(v, s.dtype);
+      bad |= !finitef(v);
+      nz |= !((-a.eps <= v) && (v <= a.eps));
+    }
+  const bool div = (__ballot(bad) & gm) != 0ull, zero = (__ballot(nz) & gm) == 0ull;
+  int8_t rs = 0;
+  if ((a.flags & SRNN_F_REMOVE_DIVERGENT) && div) rs = 1;
+  else if ((a.flags & SRNN_F_REMOVE_ZERO) && zero) rs = 2;
+  __syncthreads();
+  if (active && a.traj) ww_store(s, g, R.w, GItem::rowp(s, a.traj, k), u);  // recording: before any respawn
+  __syncthreads();
+  if (active && rs) {  // g_init: glorot per layer
+    const uint64_t key = respawn_key(gen, k);
+    for (int l = 0; l < s.NL; ++l) {
+      const int n = s.rows[l] * s.cols[l];
+      const float lim = sqrtf(6.0f / (float)(s.rows[l] + s.cols[l]));
+      for (int b = u; b < (n + 3) / 4; b += g.U) {
+        const U4 q4 = rng.draw(key, (uint32_t)s.off[l] * 1024u + (uint32_t)b, P_INIT);
+        const uint32_t xs[4] = {q4.x, q4.y, q4.z, q4.w};
+        for (int q = 0; q < 4; ++q) {
+          const int e = b * 4 + q;
+          if (e < n) R.w[ww_pidx(s, g, s.off[l] + e)] = -lim + 2.0f * lim * u01(xs[q]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (active) {
+    ww_store(s, g, R.w, GItem::rowp(s, a.W, k), u);  // E(k)
+    if (u == 0) {
+      if (a.action) a.action[k] = act;
+      if (a.counterpart) a.counterpart[k] = cp;
+      if (a.loss) a.loss[k] = loss;
+      if (a.respawn) a.respawn[k] = rs;
+    }
+  }
+}
+
+template <int WT = 0, int DT = 0>
+__global__ __launch_bounds__(64) void k_gord_run_ww(GShape s, WWave g, SrnnArgs a) {
+  extern __shared__ float sm[];
+  float* coords = sm;  // [P][3], whole workgroup
+  make_coords_dev(s, coords);
+  const int lane = threadIdx.x, u = lane % g.U, grp = lane / g.U;
+  WWGroup R = ww_group(s, g, sm, grp);
+  int32_t* s_q = reinterpret_cast<int32_t*>(sm + 3 * s.P + g.G * g.GS);  // [G] the round's records
+  const bool shuffle = (a.flags & SRNN_F_SHUFFLE) != 0;
+  const Rng rng = GItem::rng(a);
+  const unsigned long long gm = (g.U == 64 ? ~0ull : ((1ull << g.U) - 1ull)) << (grp * g.U);
+  // (SRNN_F_ORD_SYNC: this run has started, as k_ord_run counts it)
+  if ((a.flags & SRNN_F_ORD_SYNC) && blockIdx.x == 0 && lane == 0)
+    __hip_atomic_fetch_add(a.o_sync + ord::SYNC_RUN, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int32_t gen = a.gen_ptr ? a.gen_ptr[0] : a.gen;
+  // the turns of this wave's index positions that have no producer
+  int64_t cur = -1;
+  {
+    const int64_t k = (int64_t)blockIdx.x * g.G + grp;
+    if (k < a.n && a.o_list[k] < 0) cur = k;
+  }
+  if (cur >= 0 && u == 0) ord::st_level(a.o_src + 4 * cur + 3, 0);
+  int32_t ready = ord::EMPTY, nready = 0;  // (the leader lane's list of records it made ready)
+  bool raised = false;
+  for (;;) {
+    if (__ballot(cur >= 0) != 0ull) {
+      const uint64_t t0 = a.o_trace ? __builtin_amdgcn_s_memrealtime() : 0;
+      gord_ww_turn<WT, DT>(s, g, a, R, coords, u, gm, cur, gen, shuffle, rng);
+      // every row store of the wave precedes the leaders' publish in program order; its
+      // s_waitcnt vmcnt(0) is the wave's, so it covers the stores of all the group's lanes
+      if (cur >= 0 && u == 0) {
+        ord::publish(a, cur, ready, nready);
+        if (a.o_trace) {
+          a.o_trace[ord::TRACE_SLOTS * cur] = t0;
+          a.o_trace[ord::TRACE_SLOTS * cur + ord::TRACE_END] = __builtin_amdgcn_s_memrealtime();
+        }
+      }
+    }
+    // the wave's ready records, one per group (the rest stay in their lists for the next round)
+    const int32_t total = ord::wave_sum(nready);
+    if (total == 0) break;
+    int32_t pre = nready;  // exclusive prefix of the list lengths
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int32_t v = __shfl_up(pre, off);
+      if (lane >= off) pre += v;
+    }
+    pre -= nready;
+    for (int32_t t = pre; t < g.G && nready > 0; ++t) {
+      s_q[t] = ready;
+      ready = ord::pend(a, ready)[ord::R_RDY];
+      --nready;
+    }
+    __syncthreads();
+    cur = -1;
+    int32_t prow = -1;
+    if (grp < total) {
+      prow = s_q[grp];
+      cur = ord::pend(a, prow)[0];
+    }
+    __syncthreads();  // (s_q is refilled next round)
+    // the producers' rows (released before their decrements) are visible after this; rows this wave
+    // wrote in an earlier round are ordered at workgroup scope
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!raised) {
+      __builtin_amdgcn_s_setprio(2);
+      raised = true;
+    }
+    if (cur >= 0) {
+      const int32_t* rec = ord::pend(a, prow);
+      int32_t lv = 0;
+      for (int t = 0; t < rec[1]; ++t) {
+        const int32_t lp = ord::ld_level(a.o_src + 4 * (int64_t)rec[ord::R_PROD + t] + 3);
+        lv = lv > lp ? lv : lp;
+      }
+      if (u == 0) ord::st_level(a.o_src + 4 * cur + 3, lv + 1);
+    }
+  }
+}
+
+// knob SRNN_KNOB_ORD_WAVE = 0: the lane run for every shape (A/B tests)
+static bool gord_wave_serves(const GShape& s, WWave& g) {
+  if (knob(SRNN_KNOB_ORD_WAVE, 1) == 0) return false;
+  if (s.kind != 0 || s.P > GORD_MAXP) return false;
+  return ww_ord_geom(s, g) && ww_ord_lds(s, g) <= 64 * 1024;
+}
+template <int WT, int DT>
+static void gord_ww_launch_shape(dim3 grid, size_t lds, hipStream_t st, const GShape& s, const WWave& g,
+                                 const SrnnArgs& a) {
+  hipLaunchKernelGGL((k_gord_run_ww<WT, DT>), grid, dim3(64), lds, st, s, g, a);
+}
+// one wave per G turns; the register-SGD instantiations of ww_launch (SRNN_KNOB_WW_WAVE = 2: the LDS form)
+static void gord_ww_launch(const GShape& s, const WWave& g, const SrnnArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)((a.n + g.G - 1) / g.G));
+  const size_t lds = ww_ord_lds(s, g);
+  const bool reg = knob(SRNN_KNOB_WW_WAVE, 1) != 2;
+  const int w = reg ? s.W : 0, d = reg ? s.D : 0;
+  if (w == 3 && d == 3 && g.U == 4) gord_ww_launch_shape<3, 3>(grid, lds, st, s, g, a);
+  else if (w == 3 && d == 4 && g.U == 4) gord_ww_launch_shape<3, 4>(grid, lds, st, s, g, a);
+  else if (w == 10 && d == 2 && g.U == 16) gord_ww_launch_shape<10, 2>(grid, lds, st, s, g, a);
+  else if (w == 10 && d == 3 && g.U == 16) gord_ww_launch_shape<10, 3>(grid, lds, st, s, g, a);
+  else if (w == 16 && d == 2 && g.U == 16) gord_ww_launch_shape<16, 2>(grid, lds, st, s, g, a);
+  else if (w == 16 && d == 3 && g.U == 16) gord_ww_launch_shape<16, 3>(grid, lds, st, s, g, a);
+  else gord_ww_launch_shape<0, 0>(grid, lds, st, s, g, a);
+}
+
 // which runtime shapes have a reference-order generation: every valid shape on the device whose
 // Weightwise coordinate table fits the run launch's static LDS; on the host every shape but the
 // big aggregating nets (aggregating, P > 64: they have no host form)
@@ -2414,6 +2713,12 @@ static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) 
               "turn plus the critical-list waves: srnn_generic_ord_scratch_bytes)");
     return -5;
   }
+  // the wide Weightwise nets: a group of lanes per turn (the close stays lane per row; a generation
+  // whose run launch also builds the next plan, SRNN_F_ORD_INPLAN, keeps the lane run, which has
+  // the plan workgroups).  The run arguments are the generation's own: the lane run's scheduling
+  // knobs (critical list, ready queue, shadow lanes, bulk delay) do not apply to this form.
+  if (WWave g; !(a.flags & SRNN_F_ORD_INPLAN) && gord_wave_serves(s, g))
+    return ord_generation_dev_run<GOrdPol>(c, s, a, [&](hipStream_t st, int64_t) { gord_ww_launch(s, g, a, st); });
   return ord_generation_dev<GOrdPol>(c, s, a, 12, [&](hipStream_t st) {
     hipLaunchKernelGGL(k_gord_head, dim3(1), dim3(64), 0, st, s, a);
   });
@@ -2555,6 +2860,16 @@ extern "C" int64_t srnn_generic_ord_scratch_bytes(const SrnnCfg* c, int64_t n) {
   const char* why = "";
   if (!srnn::make_gshape(*c, s, &why)) return -1;
   return srnn::gord_scratch_bytes(s, n < 0 ? 0 : n);
+}
+
+// the run form of a runtime shape's reference-order generation on the host (dev 0) / device (dev 1),
+// with the knob in force: 0 none, 1 a lane per turn, 2 a group of lanes per turn (k_gord_run_ww)
+extern "C" int srnn_generic_ord_run_form(const SrnnCfg* c, int dev) {
+  srnn::GShape s;
+  const char* why = "";
+  if (!srnn::make_gshape(*c, s, &why) || !srnn::gord_serves(s, OP_SOUP_ORDERED, dev != 0, &why)) return 0;
+  srnn::WWave g;
+  return dev && srnn::gord_wave_serves(s, g) ? 2 : 1;
 }
 
 // 1 when the runtime-shape engine serves `op` of this configuration on the host (dev 0) / device

@@ -1352,11 +1352,11 @@ void ord_generation_host(const SrnnArgs& a, Turn&& turn, Close&& close_class) {
 }
 
 // device: [plan ->] run -> close [-> finish, unless the caller batches it] of the family Pol (its
-// run policy: turn and close; ca: the close's first argument).  bulk_delay: ord_run_args;
-// before_run(stream): the family's own launch ahead of the run, if any.
-template <class Pol, class BeforeRun>
-int ord_generation_dev(const SrnnCfg& c, const typename Pol::CloseArg& ca, const SrnnArgs& a, int bulk_delay,
-                       BeforeRun&& before_run) {
+// run policy: turn and close; ca: the close's first argument).  run(stream, nb): the launch(es) of
+// every turn of the generation -- k_ord_run<Pol> below, or a family's own run form over the same
+// plan, records and hand-off (srnn_generic.hip: a group of lanes per turn).
+template <class Pol, class Run>
+int ord_generation_dev_run(const SrnnCfg& c, const typename Pol::CloseArg& ca, const SrnnArgs& a, Run&& run) {
   if (!(a.flags & SRNN_F_TWO_PHASE) || !a.temp) {
     set_error("device ordered soup generation: two-phase block stats (temp) needed");
     return -5;
@@ -1365,9 +1365,7 @@ int ord_generation_dev(const SrnnCfg& c, const typename Pol::CloseArg& ca, const
   if (nb <= 0) return 0;
   hipStream_t st = (hipStream_t)a.stream;
   if (!(a.flags & SRNN_F_ORD_PLANNED)) ord_plan_dev<Pol::RB, typename Pol::PT>(c, a, false);
-  const SrnnArgs ra = ord_run_args(a, nb, bulk_delay);
-  before_run(st);
-  hipLaunchKernelGGL((k_ord_run<Pol>), dim3((unsigned)ord_run_grid(ra, nb)), dim3(TB), 0, st, c, ra);
+  run(st, nb);
   hipLaunchKernelGGL((k_ord_close<Pol>), dim3((unsigned)nb), dim3(TB), 0, st, ca, a);
   if (!(a.flags & SRNN_F_GEN_COUNTS)) {  // (the finish reads the net only for the generation counter)
     constexpr int FNT = SRNN_FINISH_NT;
@@ -1379,6 +1377,18 @@ int ord_generation_dev(const SrnnCfg& c, const typename Pol::CloseArg& ca, const
     return -3;
   }
   return 0;
+}
+
+// ... with the lane run k_ord_run<Pol>.  bulk_delay: ord_run_args; before_run(stream): the family's
+// own launch ahead of the run, if any.
+template <class Pol, class BeforeRun>
+int ord_generation_dev(const SrnnCfg& c, const typename Pol::CloseArg& ca, const SrnnArgs& a, int bulk_delay,
+                       BeforeRun&& before_run) {
+  return ord_generation_dev_run<Pol>(c, ca, a, [&](hipStream_t st, int64_t nb) {
+    const SrnnArgs ra = ord_run_args(a, nb, bulk_delay);
+    before_run(st);
+    hipLaunchKernelGGL((k_ord_run<Pol>), dim3((unsigned)ord_run_grid(ra, nb)), dim3(TB), 0, st, c, ra);
+  });
 }
 
 // OP_SOUP_ORDERED of a lane-template net

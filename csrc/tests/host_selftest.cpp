@@ -388,7 +388,18 @@ static void ordered_soup(const SrnnCfg& c, int64_t n, int gens, int pipe) {
 }
 
 int main() {
-  CHECK(srnn_abi_version() == 31);
+  CHECK(srnn_abi_version() == 32);
+  {  // the run form of a reference-order generation, with the group-run knob in force
+    const SrnnCfg w22 = ww22(), w33 = cfg(0, 3, 3, 0, 33), r32 = cfg(2, 3, 2, 0, 34), big = cfg(1, 10, 3, 4, 280);
+    CHECK(srnn_ord_run_form(&w22, 0) == 1 && srnn_ord_run_form(&w22, 1) == 1);
+    CHECK(srnn_ord_run_form(&w33, 0) == 1 && srnn_ord_run_form(&w33, 1) == 2);
+    CHECK(srnn_ord_run_form(&r32, 0) == 1 && srnn_ord_run_form(&r32, 1) == 1);
+    CHECK(srnn_generic_ord_run_form(&big, 0) == 0);  // no host form
+    srnn_set_knob(SRNN_KNOB_ORD_WAVE, 0);
+    CHECK(srnn_get_knob(SRNN_KNOB_ORD_WAVE) == 0 && srnn_ord_run_form(&w33, 1) == 1);
+    srnn_set_knob(SRNN_KNOB_ORD_WAVE, -1);
+    CHECK(srnn_get_knob(SRNN_KNOB_ORD_WAVE) == -1 && srnn_ord_run_form(&w33, 1) == 2);
+  }
   ordered_soup(ww22(), 257, 4, 0);
   ordered_soup(ww22(), 257, 4, 1);
   ordered_soup(ww22(), 257, 4, 2);

@@ -117,6 +117,8 @@ class ExecConfig:
                                             # waves wait before their first turn, the critical chain's root
                                             # ahead of the bulk (None: 12 for the lane nets, first residency
                                             # round only, measured best of 0-35; 0 for the big nets)
+    ord_wave: Optional[bool] = None         # SRNN_ORD_WAVE: reference-order turns of the wide Weightwise runtime
+                                            # shapes on a group of lanes each (None: on) or a lane each
     ordsh_emulate: int = 0                  # SRNN_ORDSH_EMULATE: one-rank timing model of R ranks of a sharded
                                             # reference-order generation (the rank runs 1/R of the turns;
                                             # the other turns never run: timing only, results invalid)
@@ -146,16 +148,16 @@ class ExecConfig:
                 force_generic="SRNN_FORCE_GENERIC", ww_wave="SRNN_WW_WAVE", rnn_wave="SRNN_RNN_WAVE",
                 rnn_spec="SRNN_RNN_SPEC", rnn_soup="SRNN_RNN_SOUP", big_wave="SRNN_BIG_WAVE",
                 fix_group="SRNN_FIX_GROUP", soup_lanes="SRNN_SOUP_LANES", ord_crit="SRNN_ORD_CRIT", ord_queue="SRNN_ORD_QUEUE",
-                ord_shadow="SRNN_ORD_SHADOW", ord_bulk_delay="SRNN_ORD_BULK_DELAY",
+                ord_shadow="SRNN_ORD_SHADOW", ord_bulk_delay="SRNN_ORD_BULK_DELAY", ord_wave="SRNN_ORD_WAVE",
                 ordsh_emulate="SRNN_ORDSH_EMULATE",
                 order_levels="SRNN_ORDER_LEVELS",
                 perm_table="SRNN_PERM_TABLE", ord_pipeline="SRNN_ORD_PIPELINE",
                 ord_census_side="SRNN_ORD_CENSUS_SIDE", ord_graph_sync="SRNN_ORD_GRAPH_SYNC")
     # Optional[bool] knobs whose None means "the built-in choice" (by population size, ...)
     TRI_STATE = ("force_generic", "rnn_wave", "rnn_spec", "rnn_soup", "big_wave", "fix_group", "perm_table",
-                 "ord_crit", "ord_queue")
+                 "ord_crit", "ord_queue", "ord_wave")
     LIBRARY_KNOBS = ("force_generic", "ww_wave", "rnn_wave", "rnn_spec", "rnn_soup", "big_wave", "fix_group",
-                     "soup_lanes", "ord_crit", "ord_queue", "ord_shadow", "ord_bulk_delay")
+                     "soup_lanes", "ord_crit", "ord_queue", "ord_shadow", "ord_bulk_delay", "ord_wave")
 
     def validate(self):
         if self.finish_mode not in ("batch", "serial"):

@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SRNN_LIB: load another build of the library (A/B of compiler flags on the GPU box)
 LIB_PATH = os.environ.get("SRNN_LIB") or os.path.join(_HERE, "libsrnn.so")
 CSRC = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc"))
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 # SrnnOp (csrc/srnn_abi.h)
 OP_INIT = 0
@@ -200,6 +200,8 @@ def lib():
         L.srnn_ord_run_lanes.restype = ctypes.c_int64
         L.srnn_generic_ord_scratch_bytes.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int64]
         L.srnn_generic_ord_scratch_bytes.restype = ctypes.c_int64
+        L.srnn_ord_run_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int]
+        L.srnn_ord_run_form.restype = ctypes.c_int
         L.srnn_big_fix_temp_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
         L.srnn_big_fix_temp_bytes.restype = ctypes.c_int64
         L.srnn_set_force_generic.argtypes = [ctypes.c_int]
@@ -269,11 +271,13 @@ def supports(spec, op: int, device: bool, dtype: int = DTYPE_FP32) -> bool:
 # execution knobs (csrc/srnn_abi.h SrnnKnob; config.py ExecConfig): the environment variable
 # of a knob, when set, overrides what is set here
 KNOBS = {"force_generic": 0, "rnn_wave": 1, "rnn_spec": 2, "rnn_soup": 3, "ww_wave": 4, "big_wave": 5,
-         "fix_group": 6, "soup_lanes": 7, "ord_crit": 8, "ord_queue": 9, "ord_shadow": 10, "ord_bulk_delay": 11}
+         "fix_group": 6, "soup_lanes": 7, "ord_crit": 8, "ord_queue": 9, "ord_shadow": 10, "ord_bulk_delay": 11,
+         "ord_wave": 12}
 KNOB_ENV = {"force_generic": "SRNN_FORCE_GENERIC", "rnn_wave": "SRNN_RNN_WAVE", "rnn_spec": "SRNN_RNN_SPEC",
             "rnn_soup": "SRNN_RNN_SOUP", "ww_wave": "SRNN_WW_WAVE", "big_wave": "SRNN_BIG_WAVE",
             "fix_group": "SRNN_FIX_GROUP", "soup_lanes": "SRNN_SOUP_LANES", "ord_crit": "SRNN_ORD_CRIT",
-            "ord_queue": "SRNN_ORD_QUEUE", "ord_shadow": "SRNN_ORD_SHADOW", "ord_bulk_delay": "SRNN_ORD_BULK_DELAY"}
+            "ord_queue": "SRNN_ORD_QUEUE", "ord_shadow": "SRNN_ORD_SHADOW", "ord_bulk_delay": "SRNN_ORD_BULK_DELAY",
+            "ord_wave": "SRNN_ORD_WAVE"}
 
 
 def streams_concurrent(side, main, device, timeout_us: int = 20000) -> bool:
@@ -343,6 +347,15 @@ def generic_ord_scratch_bytes(spec, n: int, dtype: int = DTYPE_FP32) -> int:
     """Device scratch OP_SOUP_ORDERED of a runtime shape needs for ``n`` turns: the shape header and
     the per-lane vectors of every lane of the run launch (``ord_run_lanes``)."""
     return int(lib().srnn_generic_ord_scratch_bytes(ctypes.byref(make_cfg(spec, dtype)), int(n)))
+
+
+def ord_run_form(spec, dev: bool = True, dtype_code: int = DTYPE_FP32):
+    """The run form that serves a reference-order generation of this architecture on the device
+    (``dev=True``) or the host, with the knobs in force: ``"lane"`` -- a lane per turn (k_ord_run),
+    ``"wave"`` -- a group of lanes per turn on lane-group waves (the wide Weightwise runtime shapes,
+    csrc/srnn_generic.hip k_gord_run_ww; knob ``ord_wave``), ``None`` -- no such generation."""
+    r = int(lib().srnn_ord_run_form(ctypes.byref(make_cfg(spec, dtype_code)), 1 if dev else 0))
+    return {1: "lane", 2: "wave"}.get(r)
 
 
 def big_fix_temp_bytes(spec, n: int, steps: int = 0, dense: bool = False) -> int:

@@ -660,6 +660,17 @@ class SoupEngine:
         out["critical"] = chain[::-1]
         return out
 
+    def ordered_run_form(self) -> Optional[str]:
+        """The run form of this engine's reference-order generations with the library knobs in force
+        now (``_lib.ord_run_form``): ``"lane"`` -- a lane per turn, ``"wave"`` -- a group of lanes per
+        turn (the wide Weightwise runtime shapes on the device, knob ``ord_wave``); ``None`` for an
+        engine of another order or a sharded one.  A generation whose run launch also builds the
+        next plan (``ord_pipeline="kernel"``) keeps the lane run."""
+        if self.order != "sequential" or self.dist.enabled:
+            return None
+        form = _lib.ord_run_form(self.spec, dev=self.device.type == "cuda", dtype_code=self.dtype_code)
+        return "lane" if form == "wave" and self._ord_mode == "kernel" else form
+
     def ordered_error(self) -> int:
         """This rank's reference-order error bits (ORD_ERRORS), sticky over the engine's life (0:
         none); read without communicating (``ordered_error_all``: every rank's)."""

@@ -1,11 +1,13 @@
 """Reference-order soups of runtime shapes on the device: ms per generation.
 
-For WW(3,3), WW(10,3), WW(16,2), Agg(4,4,3) and RNN(8,2) at the bench parameters (attack 0.1, learn 0.1,
+For WW(3,3), WW(10,3), WW(16,2), Agg(4,4,3), RNN(8,2) and RNN(16,2) at the bench parameters (attack 0.1, learn 0.1,
 train 20, respawn) this times one generation of ``SoupEngine(order="sequential")`` -- the
 continuation-scheduled generation with the runtime-shape turn (csrc/srnn_generic.hip GOrd) --
 eagerly and replayed from hipGraphs, and reports its dependency levels and run form (``--ord-wave
-0``: the wide Weightwise shapes' turns on one lane each instead of a group of lanes, the library
-knob SRNN_ORD_WAVE).  Beside it: the
+0``: the wide Weightwise shapes' turns on one lane each instead of a group of lanes and the wide
+Recurrent shapes' on one lane each instead of a wave, the library knob SRNN_ORD_WAVE).  RNN(16,2) is
+in the shape list but not in the default ``--shapes``: its lane steps outlast the step time limit at
+100k particles.  Beside it: the
 synchronous (Jacobi) soup of the same shape with the wave kernels on and off, and the host serial
 loop (``SequentialSoupEngine``) at 2,000 particles scaled per particle.
 
@@ -13,7 +15,7 @@ The driver runs every step in a child process of its own under a time limit and 
 first step that fails; each step prints one JSON line.  ``--markdown`` adds the table of
 profiles/ordered_runtime_shapes.md.
 
-    python bench/ordered_shapes.py [--n 100000] [--gens 3] [--shapes ww33,ww103,ww162,agg443,rnn82] [--ord-wave 0|1]
+    python bench/ordered_shapes.py [--n 100000] [--gens 3] [--shapes ww33,ww103,ww162,agg443,rnn82[,rnn162]] [--ord-wave 0|1]
 """
 from __future__ import annotations
 
@@ -31,7 +33,8 @@ PARAMS = dict(attacking_rate=0.1, learn_from_rate=0.1, train=20, learn_from_seve
               remove_zero=True, epsilon=1e-4)
 SHAPES = {"ww33": ("weightwise", (3, 3)), "ww103": ("weightwise", (10, 3)), "ww162": ("weightwise", (16, 2)),
           "agg443": ("aggregating", (4, 4, 3)),
-          "rnn82": ("recurrent", (8, 2))}
+          "rnn82": ("recurrent", (8, 2)), "rnn162": ("recurrent", (16, 2))}
+DEFAULT_SHAPES = tuple(k for k in SHAPES if k != "rnn162")
 STEPS = ("ordered-eager", "ordered-graph", "sync-waves", "sync-lanes", "host-serial")
 
 
@@ -118,11 +121,12 @@ def main():
     ap.add_argument("--n", type=int, default=100000)
     ap.add_argument("--gens", type=int, default=3)
     ap.add_argument("--host-n", type=int, default=2000)
-    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--shapes", default=",".join(DEFAULT_SHAPES))
     ap.add_argument("--steps", default=",".join(STEPS))
     ap.add_argument("--step-timeout", type=int, default=150)
     ap.add_argument("--ord-wave", type=int, choices=(0, 1), default=None,
-                    help="reference-order turns of the wide Weightwise shapes on lane groups (1) or lanes (0); "
+                    help="reference-order turns of the wide Weightwise shapes on lane groups and of the wide "
+                         "Recurrent shapes on waves (1), or on lanes (0); "
                          "default: the library's choice")
     ap.add_argument("--markdown", action="store_true")
     ap.add_argument("--child", nargs=2, metavar=("STEP", "SHAPE"))

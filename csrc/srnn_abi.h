@@ -295,7 +295,8 @@ enum SrnnKnob {
   SRNN_KNOB_ORD_BULK_DELAY = 11, // SRNN_ORD_BULK_DELAY: microseconds a reference-order run's turn waves (not the
                                  //   critical-list waves) wait before their first turn (default 12)
   SRNN_KNOB_ORD_WAVE = 12,      // SRNN_ORD_WAVE: reference-order turns of the wide Weightwise runtime shapes on a
-                                //   group of lanes each (1, default) or one lane each (0)
+                                //   group of lanes each and of the wide Recurrent ones on a wave each (1,
+                                //   default), or one lane each (0)
   SRNN_KNOB_COUNT = 13
 };
 void srnn_set_knob(int knob, int value);
@@ -311,7 +312,8 @@ int64_t srnn_ord_run_lanes(int64_t n);
 int64_t srnn_generic_ord_scratch_bytes(const SrnnCfg* cfg, int64_t n);
 int srnn_generic_supports(const SrnnCfg* cfg, int op, int dev);
 // the run form of a reference-order generation of this configuration on the host (dev 0) / device
-// (dev 1), the knobs in force counted: 0 none, 1 a lane per turn, 2 a group of lanes per turn
+// (dev 1), the knobs in force counted: 0 none, 1 a lane per turn, 2 a group of lanes (wide
+// Weightwise) or a wave (wide Recurrent) per turn
 int srnn_ord_run_form(const SrnnCfg* cfg, int dev);
 int srnn_generic_ord_run_form(const SrnnCfg* cfg, int dev);
 // temp bytes of a chunk-state run_fixpoint (big aggregating nets) over n rows: state float[n][aggregates] +

@@ -284,7 +284,8 @@ int srnn_supports(const SrnnCfg* cfg, int op, int dev) {
 
 // the run form that serves a reference-order generation of this configuration on the host (dev 0)
 // / device (dev 1), the knobs in force counted: 0 none, 1 a lane per turn (k_ord_run), 2 a group of
-// lanes per turn (the wide Weightwise runtime shapes, srnn_generic.hip)
+// lanes per turn (the wide Weightwise runtime shapes) or a wave per turn (the wide Recurrent ones,
+// both srnn_generic.hip)
 int srnn_ord_run_form(const SrnnCfg* cfg, int dev) {
   SrnnArgs probe{};
   probe.dev = dev;

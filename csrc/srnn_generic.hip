@@ -1519,9 +1519,10 @@ static void rw_launch_shape(int op, dim3 grid, size_t lds, hipStream_t st, const
     default: hipLaunchKernelGGL((k_rnn_wave<OP_RUN_FIXPOINT, WT, DT>), grid, dim3(64), lds, st, s, a); break;
   }
 }
-static bool rw_serves(int op, const GShape& s, const SrnnArgs& a) {
+// (the shape's part: also what the wave run of a reference-order generation asks, gord_rnn_serves)
+static bool rw_shape_serves(const GShape& s) {
   if (knob(SRNN_KNOB_RNN_WAVE, 1) == 0) return false;
-  if (s.kind != 2 || s.W < RW_MIN_WIDTH || s.W > 64 || rw_lds_bytes(s) > 60 * 1024 || !a.dev) return false;
+  if (s.kind != 2 || s.W < RW_MIN_WIDTH || s.W > 64 || rw_lds_bytes(s) > 60 * 1024) return false;
   // RD's closed form of the layer tables must be make_gshape's
   for (int l = 0; l < s.NL; ++l) {
     const int kl = l == 0 ? 0 : s.W + s.W * s.W + (l - 1) * 2 * s.W * s.W;
@@ -1529,7 +1530,10 @@ static bool rw_serves(int op, const GShape& s, const SrnnArgs& a) {
         s.in_[l] != (l == 0 ? 1 : s.W))
       return false;
   }
-  if (s.P != s.koff[s.D] + s.W + 1 || s.HS != s.D * s.W + 1) return false;
+  return s.P == s.koff[s.D] + s.W + 1 && s.HS == s.D * s.W + 1;
+}
+static bool rw_serves(int op, const GShape& s, const SrnnArgs& a) {
+  if (!a.dev || !rw_shape_serves(s)) return false;
   if (op == OP_SOUP_EVOLVE)  // single-rank generations (sharded exchanges: the lane path)
     return knob(SRNN_KNOB_RNN_SOUP, 1) != 0 && !(a.flags & (SRNN_F_X2 | SRNN_F_FULL_TABLE)) && a.heads && a.nexts;
   return op == OP_APPLY || op == OP_TRAIN || op == OP_LEARN || op == OP_RUN_FIXPOINT;
@@ -2659,6 +2663,184 @@ static void gord_ww_launch(const GShape& s, const WWave& g, const SrnnArgs& a, h
   else gord_ww_launch_shape<0, 0>(grid, lds, st, s, g, a);
 }
 
+// ----------------------------------------------------------------------------------------------
+// The wave run of the wide Recurrent nets (k_gord_run_rnn): a reference-order turn on the wave-per-
+// particle arithmetic of k_rnn_wave_soup (rw_forward, rw_train_epoch: the weights, the gradients and
+// the sequence in LDS, lane j the unit j of a layer) instead of one lane of GOrd::turn, whose every
+// weight, hidden state and BPTT state goes through the element-major scratch in HBM.  One wave per
+// workgroup, one turn per wave at a time, one workgroup per index position.  The turn is GOrd::turn
+// step for step (recompute depth 0) on the three LDS row vectors r.w (o_w), r.aux (o_o) and r.seq
+// (o_t), and the dot products keep the lane path's order, so a generation is bitwise the lane run's.
+//
+// The schedule is k_gord_run_ww's with G = 1: the wave of an index position that has no producer
+// runs that root once, lane 0 publishes (ord::publish, after every row store of the wave), the wave
+// takes one record from the list lane 0 made ready and runs it at level 1 + the deepest producer's,
+// until its list is empty.  No wave waits for another; no critical list, ready queue, shadow lanes,
+// bulk delay, census workgroups or in-run plan.
+//
+// Scratch: workgroup b owns the slice b * rw_soup_scratch_bytes(s) after the header (BPTT states,
+// orthogonal-init doubles of a respawn) of the scratch the lane run would use (gord_rnn_fits).
+// LDS: rw_layout's regions, then the handed-out record.
+static size_t gord_rnn_lds(const GShape& s) { return rw_lds_bytes(s) + 16; }
+
+// turn k on the whole wave
+template <int WT, int DT>
+__device__ __forceinline__ void gord_rnn_turn(const GShape& s, const SrnnArgs& a, const RWave& r, float* hs,
+                                              double* orth, int64_t k, int32_t gen) {
+  const int lane = threadIdx.x;
+  const int32_t* sc = a.o_src + 4 * k;
+  int64_t at, te;
+  GOrd::Dec::decision(a, k, gen, at, te);
+  if (const char* row = gw_version(s, a, sc[0])) rw_load(s, row, r.w);
+  rw_sync();
+  int8_t act = A_NONE;
+  int64_t cp = -1;
+  if (at >= 0) {  // 1. attack: A(k) = f_k(victim), the own net over the victim's weight sequence
+    if (ord::needs_A(a, k, sc)) {
+      if (at == k) {
+        for (int q = lane; q < s.P; q += 64) r.seq[q] = r.w[q];
+      } else if (const char* row = gw_version(s, a, sc[1])) {
+        rw_load(s, row, r.seq);
+      }
+      rw_sync();
+      rw_forward<WT, DT>(s, r, r.w, r.seq, nullptr, r.aux);
+      rw_quant(s, r.aux);
+      rw_sync();
+      if (ord::stored(a, k)) rw_store(s, GItem::rowp(s, a.W3, k), r.aux);
+      if (at == k) {
+        for (int q = lane; q < s.P; q += 64) r.w[q] = r.aux[q];
+        rw_sync();
+      }
+    }
+    act = A_ATTACKING;
+    cp = at;
+  }
+  float loss = 0.f;
+  if (te >= 0) {  // 2. learn_from the teacher's current row (the gradients reuse r.aux: the copy is first)
+    if (sc[2] == ord::SRC_SELF) {
+      for (int q = lane; q < s.P; q += 64) r.seq[q] = r.w[q];
+    } else if (sc[2] == ord::SRC_ATK) {
+      for (int q = lane; q < s.P; q += 64) r.seq[q] = r.aux[q];
+    } else if (const char* row = gw_version(s, a, sc[2])) {
+      rw_load(s, row, r.seq);
+    }
+    rw_sync();
+    for (int e = 0; e < a.severity; ++e) loss = rw_train_epoch<WT, DT>(s, r, hs, a.lr);
+    act = A_LEARN_FROM;
+    cp = te;
+  }
+  if (a.epochs > 0) {  // 3. self-train: the samples are the weights at each epoch start
+    for (int e = 0; e < a.epochs; ++e) {
+      for (int q = lane; q < s.P; q += 64) r.seq[q] = r.w[q];
+      rw_sync();
+      loss = rw_train_epoch<WT, DT>(s, r, hs, a.lr);
+    }
+    act = A_TRAIN_SELF;
+    cp = -1;
+  }
+  rw_quant(s, r.w);  // 4. respawn (the stored state decides)
+  rw_sync();
+  int8_t rs = 0;
+  if ((a.flags & SRNN_F_REMOVE_DIVERGENT) && rw_diverged(s, r.w)) rs = 1;
+  else if ((a.flags & SRNN_F_REMOVE_ZERO) && rw_zero(s, r.w, a.eps)) rs = 2;
+  if (a.traj) rw_store(s, GItem::rowp(s, a.traj, k), r.w);  // recording: the state before any respawn
+  if (rs) {
+    rw_sync();
+    if (lane == 0) {
+      const GCtx x{&s, nullptr, 1, nullptr, orth};
+      g_init(x, SV{r.w, 1}, GItem::rng(a), respawn_key(gen, k));
+    }
+    rw_sync();
+  }
+  rw_store(s, GItem::rowp(s, a.W, k), r.w);  // E(k)
+  if (lane == 0) {
+    if (a.action) a.action[k] = act;
+    if (a.counterpart) a.counterpart[k] = cp;
+    if (a.loss) a.loss[k] = loss;
+    if (a.respawn) a.respawn[k] = rs;
+  }
+}
+
+template <int WT, int DT>
+__global__ __launch_bounds__(64) void k_gord_run_rnn(GShape s, SrnnArgs a) {
+  extern __shared__ float sm[];
+  const RWave r = rw_layout(s, sm);
+  int32_t* s_q = reinterpret_cast<int32_t*>(sm + 3 * s.P + 6 * s.HS + 128);  // the handed-out record
+  const int lane = threadIdx.x;
+  char* scr = reinterpret_cast<char*>(gord_lanes_base(a)) + (int64_t)blockIdx.x * rw_soup_scratch_bytes(s);
+  float* hs = reinterpret_cast<float*>(scr);
+  double* orth = reinterpret_cast<double*>(scr + (((int64_t)s.P * s.HS + 1) & ~(int64_t)1) * 4);
+  // (SRNN_F_ORD_SYNC: this run has started, as k_ord_run counts it)
+  if ((a.flags & SRNN_F_ORD_SYNC) && blockIdx.x == 0 && lane == 0)
+    __hip_atomic_fetch_add(a.o_sync + ord::SYNC_RUN, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int32_t gen = a.gen_ptr ? a.gen_ptr[0] : a.gen;
+  // the turn of this wave's index position, if it has no producer
+  int64_t cur = -1;
+  if ((int64_t)blockIdx.x < a.n && a.o_list[blockIdx.x] < 0) cur = blockIdx.x;
+  if (cur >= 0 && lane == 0) ord::st_level(a.o_src + 4 * cur + 3, 0);
+  int32_t ready = ord::EMPTY, nready = 0;  // (lane 0's list of records it made ready)
+  bool raised = false;
+  while (cur >= 0) {
+    const uint64_t t0 = a.o_trace ? __builtin_amdgcn_s_memrealtime() : 0;
+    gord_rnn_turn<WT, DT>(s, a, r, hs, orth, cur, gen);
+    // every row store of the wave precedes lane 0's publish in program order; its s_waitcnt
+    // vmcnt(0) is the wave's, so it covers the stores of all lanes
+    if (lane == 0) {
+      ord::publish(a, cur, ready, nready);
+      if (a.o_trace) {
+        a.o_trace[ord::TRACE_SLOTS * cur] = t0;
+        a.o_trace[ord::TRACE_SLOTS * cur + ord::TRACE_END] = __builtin_amdgcn_s_memrealtime();
+      }
+      s_q[0] = nready > 0 ? ready : ord::EMPTY;  // one record for the wave, the rest stay listed
+      if (nready > 0) {
+        ready = ord::pend(a, ready)[ord::R_RDY];
+        --nready;
+      }
+    }
+    __syncthreads();
+    const int32_t prow = s_q[0];
+    __syncthreads();  // (s_q is rewritten after the next turn)
+    if (prow == ord::EMPTY) break;
+    const int32_t* rec = ord::pend(a, prow);
+    cur = rec[0];
+    // the producers' rows (released before their decrements) are visible after this; rows this wave
+    // wrote in an earlier turn are ordered at workgroup scope
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!raised) {
+      __builtin_amdgcn_s_setprio(2);
+      raised = true;
+    }
+    int32_t lv = 0;
+    for (int t = 0; t < rec[1]; ++t) {
+      const int32_t lp = ord::ld_level(a.o_src + 4 * (int64_t)rec[ord::R_PROD + t] + 3);
+      lv = lv > lp ? lv : lp;
+    }
+    if (lane == 0) ord::st_level(a.o_src + 4 * cur + 3, lv + 1);
+  }
+}
+
+// the Recurrent shapes of the wave run: rw_serves' shape conditions and the knob SRNN_KNOB_ORD_WAVE
+static bool gord_rnn_serves(const GShape& s) { return knob(SRNN_KNOB_ORD_WAVE, 1) != 0 && rw_shape_serves(s); }
+// ... whose n slices fit the scratch of the lane run (gord_scratch_bytes: what the engine allocates)
+static bool gord_rnn_fits(const GShape& s, int64_t n) {
+  return n * rw_soup_scratch_bytes(s) <= gord_scratch_bytes(s, n) - GORD_HDR;
+}
+// one wave per index position; rw_launch's instantiations (SRNN_KNOB_RNN_SPEC = 0: the runtime shape)
+static void gord_rnn_launch(const GShape& s, const SrnnArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)a.n), block(64);
+  const size_t lds = gord_rnn_lds(s);
+  const bool spec = knob(SRNN_KNOB_RNN_SPEC, 1) != 0;
+  const int w = spec ? s.W : 0, d = spec ? s.D : 0;
+  if (w == 8 && d == 2) hipLaunchKernelGGL((k_gord_run_rnn<8, 2>), grid, block, lds, st, s, a);
+  else if (w == 16 && d == 2) hipLaunchKernelGGL((k_gord_run_rnn<16, 2>), grid, block, lds, st, s, a);
+  else if (w == 32 && d == 2) hipLaunchKernelGGL((k_gord_run_rnn<32, 2>), grid, block, lds, st, s, a);
+  else if (w == 8 && d == 3) hipLaunchKernelGGL((k_gord_run_rnn<8, 3>), grid, block, lds, st, s, a);
+  else if (w == 16 && d == 3) hipLaunchKernelGGL((k_gord_run_rnn<16, 3>), grid, block, lds, st, s, a);
+  else hipLaunchKernelGGL((k_gord_run_rnn<0, 0>), grid, block, lds, st, s, a);
+}
+
 // which runtime shapes have a reference-order generation: every valid shape on the device whose
 // Weightwise coordinate table fits the run launch's static LDS; on the host every shape but the
 // big aggregating nets (aggregating, P > 64: they have no host form)
@@ -2719,6 +2901,10 @@ static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) 
   // knobs (critical list, ready queue, shadow lanes, bulk delay) do not apply to this form.
   if (WWave g; !(a.flags & SRNN_F_ORD_INPLAN) && gord_wave_serves(s, g))
     return ord_generation_dev_run<GOrdPol>(c, s, a, [&](hipStream_t st, int64_t) { gord_ww_launch(s, g, a, st); });
+  // the wide Recurrent nets: a wave per turn, under the same conditions, where the waves' BPTT
+  // states fit the scratch of the lane run (else the lane run)
+  if (!(a.flags & SRNN_F_ORD_INPLAN) && gord_rnn_serves(s) && gord_rnn_fits(s, a.n))
+    return ord_generation_dev_run<GOrdPol>(c, s, a, [&](hipStream_t st, int64_t) { gord_rnn_launch(s, a, st); });
   return ord_generation_dev<GOrdPol>(c, s, a, 12, [&](hipStream_t st) {
     hipLaunchKernelGGL(k_gord_head, dim3(1), dim3(64), 0, st, s, a);
   });
@@ -2863,13 +3049,15 @@ extern "C" int64_t srnn_generic_ord_scratch_bytes(const SrnnCfg* c, int64_t n) {
 }
 
 // the run form of a runtime shape's reference-order generation on the host (dev 0) / device (dev 1),
-// with the knob in force: 0 none, 1 a lane per turn, 2 a group of lanes per turn (k_gord_run_ww)
+// with the knob in force: 0 none, 1 a lane per turn, 2 a wave run -- a group of lanes per turn
+// (k_gord_run_ww, the wide Weightwise nets) or a wave per turn (k_gord_run_rnn, the wide Recurrent
+// nets; a population whose BPTT states do not fit the lane run's scratch still takes the lane run)
 extern "C" int srnn_generic_ord_run_form(const SrnnCfg* c, int dev) {
   srnn::GShape s;
   const char* why = "";
   if (!srnn::make_gshape(*c, s, &why) || !srnn::gord_serves(s, OP_SOUP_ORDERED, dev != 0, &why)) return 0;
   srnn::WWave g;
-  return dev && srnn::gord_wave_serves(s, g) ? 2 : 1;
+  return dev && (srnn::gord_wave_serves(s, g) || srnn::gord_rnn_serves(s)) ? 2 : 1;
 }
 
 // 1 when the runtime-shape engine serves `op` of this configuration on the host (dev 0) / device

@@ -395,10 +395,14 @@ int main() {
     CHECK(srnn_ord_run_form(&w33, 0) == 1 && srnn_ord_run_form(&w33, 1) == 2);
     CHECK(srnn_ord_run_form(&r32, 0) == 1 && srnn_ord_run_form(&r32, 1) == 1);
     CHECK(srnn_generic_ord_run_form(&big, 0) == 0);  // no host form
+    const SrnnCfg r82 = cfg(2, 8, 2, 0, 209);  // Recurrent(8,2): a wave per turn
+    CHECK(srnn_ord_run_form(&r82, 0) == 1 && srnn_ord_run_form(&r82, 1) == 2);
     srnn_set_knob(SRNN_KNOB_ORD_WAVE, 0);
     CHECK(srnn_get_knob(SRNN_KNOB_ORD_WAVE) == 0 && srnn_ord_run_form(&w33, 1) == 1);
+    CHECK(srnn_ord_run_form(&r82, 1) == 1);
     srnn_set_knob(SRNN_KNOB_ORD_WAVE, -1);
     CHECK(srnn_get_knob(SRNN_KNOB_ORD_WAVE) == -1 && srnn_ord_run_form(&w33, 1) == 2);
+    CHECK(srnn_ord_run_form(&r82, 1) == 2);
   }
   ordered_soup(ww22(), 257, 4, 0);
   ordered_soup(ww22(), 257, 4, 1);

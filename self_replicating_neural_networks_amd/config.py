@@ -118,7 +118,8 @@ class ExecConfig:
                                             # ahead of the bulk (None: 12 for the lane nets, first residency
                                             # round only, measured best of 0-35; 0 for the big nets)
     ord_wave: Optional[bool] = None         # SRNN_ORD_WAVE: reference-order turns of the wide Weightwise runtime
-                                            # shapes on a group of lanes each (None: on) or a lane each
+                                            # shapes on a group of lanes each and of the wide Recurrent ones
+                                            # (width >= 8) on a wave each (None: on), or a lane each
     ordsh_emulate: int = 0                  # SRNN_ORDSH_EMULATE: one-rank timing model of R ranks of a sharded
                                             # reference-order generation (the rank runs 1/R of the turns;
                                             # the other turns never run: timing only, results invalid)

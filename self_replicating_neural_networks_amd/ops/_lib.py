@@ -353,7 +353,8 @@ def ord_run_form(spec, dev: bool = True, dtype_code: int = DTYPE_FP32):
     """The run form that serves a reference-order generation of this architecture on the device
     (``dev=True``) or the host, with the knobs in force: ``"lane"`` -- a lane per turn (k_ord_run),
     ``"wave"`` -- a group of lanes per turn on lane-group waves (the wide Weightwise runtime shapes,
-    csrc/srnn_generic.hip k_gord_run_ww; knob ``ord_wave``), ``None`` -- no such generation."""
+    csrc/srnn_generic.hip k_gord_run_ww) or a whole wave per turn (the Recurrent nets of width >= 8,
+    k_gord_run_rnn; both under the knob ``ord_wave``), ``None`` -- no such generation."""
     r = int(lib().srnn_ord_run_form(ctypes.byref(make_cfg(spec, dtype_code)), 1 if dev else 0))
     return {1: "lane", 2: "wave"}.get(r)
 

@@ -663,7 +663,8 @@ class SoupEngine:
     def ordered_run_form(self) -> Optional[str]:
         """The run form of this engine's reference-order generations with the library knobs in force
         now (``_lib.ord_run_form``): ``"lane"`` -- a lane per turn, ``"wave"`` -- a group of lanes per
-        turn (the wide Weightwise runtime shapes on the device, knob ``ord_wave``); ``None`` for an
+        turn (the wide Weightwise runtime shapes) or a wave per turn (the Recurrent nets of width >= 8),
+        both on the device under the knob ``ord_wave``; ``None`` for an
         engine of another order or a sharded one.  A generation whose run launch also builds the
         next plan (``ord_pipeline="kernel"``) keeps the lane run."""
         if self.order != "sequential" or self.dist.enabled:

@@ -217,6 +217,19 @@ def test_mfma_weightwise_identity_fixpoint(cuda):
     before = W.clone()
     cls, _, _ = K.run_fixpoint(spec, W, 5, 1e-4, early_exit=False)
     assert torch.equal(W, before) and cls.tolist() == [O.C_FIX_OTHER] * 4
+    # the negated twin f(x) = -x[0]: not a fixpoint, f(f(w)) = w exactly -- a second-order fixpoint;
+    # self-application negates all three kernels, (-1)**3 = -1: the identity again after one step
+    N = before.clone()
+    N[:, 0] = -1.0
+    cls, _ = K.classify(spec, N, 1e-4)
+    assert cls.tolist() == [O.C_FIX_SEC] * 4
+    assert K.classify(spec, N, 1e-4, with_sec=False)[0].tolist() == [O.C_OTHER] * 4
+    start = N.clone()
+    cls, nsteps, _ = K.run_fixpoint(spec, N, 5, 1e-4, early_exit=True)
+    assert torch.equal(N, -start) and nsteps.tolist() == [1] * 4 and cls.tolist() == [O.C_FIX_OTHER] * 4
+    out = torch.zeros_like(N)
+    K.apply(spec, N, out)
+    assert torch.equal(out, N)  # f(x) = (1)(-1)(-1) x[0]: the identity function
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])

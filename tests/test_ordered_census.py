@@ -8,11 +8,12 @@ packed class counts the close (or a deferred census) left in the block stats -- 
 
 and counts[5] (the respawn ballots, word 0 of the block stats) must equal the respawn flags set and
 the advance of next_uid.  The HOT soup of tests/test_ordered_soup.py only ever shows fix_zero and
-other (a few divergent for the RNN), so a second, seeded Weightwise(2, 2) population keeps four
-classes non-empty: zero rows, NaN rows, the identity fixpoint and small perturbations of it.
-fix_sec stays empty everywhere: the project has no constructed period-2 row, so a wrong count in the
-high half of block-stat word 2 alone would still pass.  The device counterpart is
-tests/test_ordered_census_gpu.py."""
+other (a few divergent for the RNN), so a second, seeded Weightwise(2, 2) population keeps all five
+classes non-empty: zero rows, NaN rows, the identity fixpoint, small perturbations of it, and the
+negated identity f(x) = -x, an exact second-order fixpoint (tests/classify_rows.py) -- the high half of
+block-stat word 2.  Every fourth row starts as one; enough of them stay unattacked for fix_sec to
+be non-empty at each of the 17 first generations at every size of SIZES.  The device counterpart
+is tests/test_ordered_census_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -25,6 +26,7 @@ from self_replicating_neural_networks_amd.oracle import core as oc
 from self_replicating_neural_networks_amd.seq_soup import SequentialSoupEngine
 from self_replicating_neural_networks_amd.setups.experiments import identity_fixpoint_weights
 from self_replicating_neural_networks_amd.soup_engine import SoupEngine
+from classify_rows import path_row
 from test_ordered_soup import HOT, IDS, SPECS, _same
 
 WW = ArchSpec.weightwise(2, 2)
@@ -36,12 +38,14 @@ SEED = 5
 
 
 def seeded_rows(n: int) -> torch.Tensor:
-    """The seeded Weightwise(2, 2) population: the keyed initial rows with zero rows, NaN rows, identity
-    fixpoints and fixpoints perturbed by 3e-5 * randn written over them (later writes win)."""
+    """The seeded Weightwise(2, 2) population: the keyed initial rows with negated identities (fix_sec),
+    zero rows, NaN rows, identity fixpoints and fixpoints perturbed by 3e-5 * randn written over them
+    (later writes win)."""
     W = torch.zeros((n, WW.PP), dtype=torch.float32)
     K.init_rows(WW, W, torch.arange(n, dtype=torch.int64), SEED)
     W = W[:, :WW.P].clone()
     fix = torch.from_numpy(identity_fixpoint_weights())
+    W[2::4] = torch.from_numpy(path_row(WW, -1.0, 1.0, 0))
     W[0::7] = 0.0
     W[1::11, 0] = float("nan")
     W[3::5] = fix
@@ -70,7 +74,7 @@ def population(kind, n, device="cpu", **kw):
 def check_census(o, s, uid_before=None, with_sec=True, min_classes=1, numpy_rows=False):
     """Every identity of the module docstring after an evolve call; ``uid_before``: next_uid before
     a one-generation call; ``min_classes``: non-empty classes the oracle's census must show (a
-    population collapsed to one class cannot pass a four-class test)."""
+    population collapsed to one class cannot pass a five-class test)."""
     n = o.n
     got = o.last_census()
     want = s.count(with_sec=with_sec)
@@ -104,7 +108,7 @@ def test_host_ordered_census_equals_independent_oracles(pipe, kind, n):
         o.evolve(1)
         s.evolve(1)
         _same(o, s, o.spec.P)
-        check_census(o, s, uid_before=uid0, min_classes=4 if seeded else 1, numpy_rows=True)
+        check_census(o, s, uid_before=uid0, min_classes=5 if seeded else 1, numpy_rows=True)
         deep = max(deep, o.ordered_levels()["max_level"])
     if n == 3000 and not seeded:
         assert deep >= 2  # real dependency chains
@@ -120,7 +124,10 @@ def test_host_ordered_census_without_second_order_fixpoints():
     for k in (1, 3):
         o.evolve(k)
         s.evolve(k)
-        check_census(o, s, with_sec=False, min_classes=4, numpy_rows=True)
+        got = check_census(o, s, with_sec=False, min_classes=4, numpy_rows=True)
+        # the second-order fixpoints are there and are counted as other
+        sec = s.count(with_sec=True)
+        assert got["fix_sec"] == 0 < sec["fix_sec"] and got["other"] == sec["other"] + sec["fix_sec"]
 
 
 def test_deferred_census_without_batched_finish_is_rejected():
@@ -141,7 +148,7 @@ def test_deferred_census_without_batched_finish_is_rejected():
     o.evolve(1)
     s.evolve(1)
     _same(o, s, o.spec.P)
-    check_census(o, s, min_classes=4)
+    check_census(o, s, min_classes=5)
 
 
 def test_census_log_needs_the_batched_finish():

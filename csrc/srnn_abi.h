@@ -90,7 +90,8 @@ struct SrnnArgs {
   int32_t steps;        // fixpoint run: step limit; batched finish: generations
   int32_t epochs;       // train: epochs; soup: train count
   int32_t severity;     // soup: learn_from_severity
-  int32_t early_exit;   // fixpoint run: stop at fixpoint / divergence
+  int32_t early_exit;   // fixpoint run: stop at fixpoint / divergence; mixed run: 1 = check before every
+                        // step, 2 = step 0 unchecked
   uint32_t flags;       // SrnnFlag bits
   int32_t gen;          // soup generation (time) when gen_ptr is null
   float eps;
@@ -256,6 +257,9 @@ enum SrnnOp {
                            // (srnn_ordered_sh.h)
   OP_ORD_CENSUS = 25,   // the census of a reference-order generation's final rows (W) into the class counts
                         // of its two-phase block stats (temp), after a close with SRNN_F_ORD_CENSUS_LATER
+  OP_RUN_MIXED = 26,    // mixed run per row (in place): up to `steps` times one self-attack + `epochs`
+                        // self-train epochs, until divergent or a fixpoint; counter stride epochs + 2
+                        // per step; cls + nsteps (+loss, +traj) as OP_RUN_FIXPOINT
   OP_ORD_PLAN = 24,     // the plan of a single-rank reference-order generation into o_src / o_list /
                         // o_ctl / ptab: its attack lists linked into heads / nexts (NIL on entry),
                         // source versions, stored-output marks, pending records + consumer lists
@@ -316,6 +320,15 @@ int srnn_generic_supports(const SrnnCfg* cfg, int op, int dev);
 // Weightwise) or a wave (wide Recurrent) per turn
 int srnn_ord_run_form(const SrnnCfg* cfg, int dev);
 int srnn_generic_ord_run_form(const SrnnCfg* cfg, int dev);
+// the kernel family that serves OP_TRAIN of this configuration on the host (dev 0) / device (dev 1),
+// the knobs in force counted: 0 none, 1 a lane per particle, 2 a wave / row kernel (the wide
+// Weightwise and Recurrent runtime shapes, the big aggregating nets)
+int srnn_train_form(const SrnnCfg* cfg, int dev);
+int srnn_generic_train_form(const SrnnCfg* cfg, int dev);
+// the form kernels.run_mixed takes for `epochs` self-train epochs per step: 0 none, 1 the fused
+// OP_RUN_MIXED launch, 2 the op sequence (wave / row-kernel training; on the device also long
+// training steps of the lane shapes, by measurement: srnn_common.hip)
+int srnn_mixed_form(const SrnnCfg* cfg, int dev, int epochs);
 // temp bytes of a chunk-state run_fixpoint (big aggregating nets) over n rows: state float[n][aggregates] +
 // flags int8[n]; dense != 0: + (16-byte aligned) the chunk-state trajectory float[steps][n][aggregates]
 // that a dense recording is expanded from

@@ -80,6 +80,7 @@ const char* op_name(int op) {
     case OP_SOUP_ORDERED_SH: return "srnn:soup_ordered_sh";
     case OP_ORD_PLAN: return "srnn:ord_plan";
     case OP_ORD_CENSUS: return "srnn:ord_census";
+    case OP_RUN_MIXED: return "srnn:run_mixed";
     default: return "srnn:op";
   }
 }
@@ -132,7 +133,14 @@ int knob(int id, int dflt) {
 }  // namespace srnn
 static bool force_generic() { return srnn::knob(SRNN_KNOB_FORCE_GENERIC, 0) == 1; }
 
-// which engine serves (op, cfg, host/device): 0 specialised, 1 generic, -1 none
+// the kernel family of an instantiated shape: 0 lane per particle (every op, host and device), 1 the big
+// aggregating nets' row / wave kernels, 2 the wide Weightwise wave kernels
+static int special_family(const SrnnCfg* c) {
+  return c->kind == 1 && c->p > 64 ? 1 : (c->kind == 0 && c->width >= 16 ? 2 : 0);
+}
+
+// which engine serves (op, cfg, host/device): 0 specialised, 1 generic, -1 none.  OP_RUN_MIXED has no
+// wave / row-kernel form: for those shapes it falls through to the runtime-shape lane engine
 static int route(int op, const SrnnCfg* c, const SrnnArgs* a) {
   if (!force_generic()) {
     SrnnArgs probe{};
@@ -140,7 +148,7 @@ static int route(int op, const SrnnCfg* c, const SrnnArgs* a) {
     const int r = dispatch_special(-1, c, &probe);
     if (r == 0) {
       // instantiated: does the specialised path provide this op (on this side)?
-      const int k = c->kind == 1 && c->p > 64 ? 1 : (c->kind == 0 && c->width >= 16 ? 2 : 0);
+      const int k = special_family(c);
       if (k == 0) return 0;  // lane-per-particle templates: every op, host and device
       const bool host = a && !a->dev;
       if (host) return 1;  // wave-per-particle paths are GPU only
@@ -292,6 +300,32 @@ int srnn_ord_run_form(const SrnnCfg* cfg, int dev) {
   const int r = route(OP_SOUP_ORDERED, cfg, &probe);
   if (r == 0) return 1;
   return r == 1 ? srnn_generic_ord_run_form(cfg, dev) : 0;
+}
+
+// the kernel family that serves OP_TRAIN of this configuration on the host (dev 0) / device (dev 1),
+// the knobs in force counted: 0 none, 1 a lane per particle (the lane templates, k_generic), 2 a wave
+// or row kernel (k_big_rows / k_big, k_ww_wave, k_rnn_wave).  A mixed run (OP_RUN_MIXED) is fused on
+// the lane forms; where training has a wave / row kernel the op sequence keeps that kernel
+int srnn_train_form(const SrnnCfg* cfg, int dev) {
+  SrnnArgs probe{};
+  probe.dev = dev;
+  const int r = route(OP_TRAIN, cfg, &probe);
+  if (r == 0) return special_family(cfg) == 0 ? 1 : 2;
+  return r == 1 ? srnn_generic_train_form(cfg, dev) : 0;
+}
+
+// the form of a mixed run with `epochs` self-train epochs per step: 0 none, 1 the fused OP_RUN_MIXED
+// launch, 2 the op sequence on compacted tables.  Wave / row-kernel training: the op sequence.  Lane
+// training on the host: fused.  Lane training on the device: fused while a step's training is short;
+// from a measured number of epochs on the op sequence -- a wave whose rows have mostly stopped runs its
+// epochs 4-5x slower on the few lanes left than a full wave does (profiles/mixed_run.md), and only the
+// op sequence compacts the rows still running.  Crossings at 100k rows on the MI355X: Recurrent(2,2)
+// ~29 epochs, Weightwise(2,2) ~220, Aggregating(4,2,2) beyond 500 (fused at every measured count)
+int srnn_mixed_form(const SrnnCfg* cfg, int dev, int epochs) {
+  const int f = srnn_train_form(cfg, dev);
+  if (f != 1 || !dev) return f;
+  const int limit = cfg->kind == 2 ? 32 : (cfg->kind == 0 ? 256 : INT_MAX);
+  return epochs >= limit ? 2 : 1;
 }
 
 int srnn_run(int op, const SrnnCfg* cfg, const SrnnArgs* a) {

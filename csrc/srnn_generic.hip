@@ -672,6 +672,38 @@ struct GItem {
     a.nsteps[i] = tts;
     a.loss[i] = (float)taf;
   }
+  // mixed run of row i (Item::run_mixed: the same loop, counters and rounding); w in o_w, the
+  // attack's output in o_o, the epochs' frozen samples in o_t (g_train_epochs)
+  SRNN_HD static void run_mixed(const GCtx& x, const SrnnArgs& a, int64_t i) {
+    const GShape& s = *x.s;
+    SV w = x.v(s.o_w), nw = x.v(s.o_o);
+    g_load(s, rowp(s, a.W, i), w);
+    const uint64_t uid = uid_of(a, i);
+    ApplyCtx ac = actx(a, s, uid, a.ctr);
+    TrainCtx tc = tctx(a, s, uid, a.ctr);
+    if (a.traj) g_store(s, rowp(s, a.traj, i), w);
+    const uint32_t stride = (uint32_t)a.epochs + 2u;
+    float loss = 0.f;
+    int st = 0;
+    for (; st < a.steps; ++st) {
+      const bool check = st > 0 || a.early_exit == 1;
+      if (check && g_diverged(s, w)) break;
+      g_apply(x, w, w, nw, ac);
+      g_quant(s, nw);
+      if (check && !g_diverged(s, nw) && g_within(s, nw, w, a.eps)) break;
+      g_copy(s, w, nw);
+      tc.ctr = ac.ctr + 1u;
+      if (a.epochs > 0) loss = g_train_epochs(x, w, w, a.epochs, true, tc);
+      g_quant(s, w);
+      ac.ctr += stride;
+      if (a.traj) g_store(s, rowp(s, a.traj, (int64_t)(st + 1) * a.n + i), w);
+    }
+    if (st > 0) g_store(s, rowp(s, a.W, i), w);
+    if (a.nsteps) a.nsteps[i] = st;
+    ac.ctr = a.ctr + (uint32_t)a.steps * stride;
+    if (a.cls) a.cls[i] = g_classify_w(x, w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, ac);
+    if (a.loss) a.loss[i] = loss;
+  }
   SRNN_HD static void perturb(const GCtx& x, const SrnnArgs& a, int64_t i) {
     const GShape& s = *x.s;
     SV w = x.v(s.o_w);
@@ -848,6 +880,8 @@ __global__ __launch_bounds__(GTB) void k_generic(GShape s, SrnnArgs a, int64_t l
       if (on) GItem::perturb(x, a, i);
     } else if constexpr (OP == OP_VARY_RUN) {
       if (on) GItem::vary_run(x, a, i);
+    } else if constexpr (OP == OP_RUN_MIXED) {
+      if (on) GItem::run_mixed(x, a, i);
     } else if constexpr (OP == OP_RESPAWN) {
       if (on) GItem::respawn(x, a, i);
     } else if constexpr (OP == OP_CLASSIFY || OP == GOP_CLASSIFY_COUNT) {
@@ -980,6 +1014,7 @@ static void host_generic(int op, const GShape& s, const SrnnArgs& a) {
     case OP_LEARN: host_parallel(a.n, with_ctx([&](const GCtx& x, int64_t i) { GItem::train(x, a, i, true); })); break;
     case OP_PERTURB: host_parallel(a.n, with_ctx([&](const GCtx& x, int64_t i) { GItem::perturb(x, a, i); })); break;
     case OP_VARY_RUN: host_parallel(a.n, with_ctx([&](const GCtx& x, int64_t i) { GItem::vary_run(x, a, i); })); break;
+    case OP_RUN_MIXED: host_parallel(a.n, with_ctx([&](const GCtx& x, int64_t i) { GItem::run_mixed(x, a, i); })); break;
     case OP_RESPAWN: host_parallel(a.n, with_ctx([&](const GCtx& x, int64_t i) { GItem::respawn(x, a, i); })); break;
     case OP_SOUP_EVOLVE: {
       if (a.flags & SRNN_F_X2) {
@@ -1576,7 +1611,7 @@ static bool generic_op_supported(int op) {
   switch (op) {
     case OP_INIT: case OP_APPLY: case OP_RUN_FIXPOINT: case OP_TRAIN: case OP_LEARN: case OP_CLASSIFY:
     case OP_PERTURB: case OP_SOUP_DECIDE: case OP_RESPAWN_SEQ: case OP_SOUP_EVOLVE: case OP_RESPAWN:
-    case OP_VARY_RUN:
+    case OP_VARY_RUN: case OP_RUN_MIXED:
       return true;
     default: return false;
   }
@@ -2958,6 +2993,7 @@ static int generic_launch(int op, const GShape& s, const SrnnArgs& a) {
       case OP_LEARN: SRNN_GK(OP_LEARN)
       case OP_PERTURB: SRNN_GK(OP_PERTURB)
       case OP_VARY_RUN: SRNN_GK(OP_VARY_RUN)
+      case OP_RUN_MIXED: SRNN_GK(OP_RUN_MIXED)
       case OP_RESPAWN: SRNN_GK(OP_RESPAWN)
       case OP_SOUP_EVOLVE:
         if ((a.flags & SRNN_F_X2) && (a.flags & SRNN_F_X2_REMOTE)) {
@@ -3058,6 +3094,20 @@ extern "C" int srnn_generic_ord_run_form(const SrnnCfg* c, int dev) {
   if (!srnn::make_gshape(*c, s, &why) || !srnn::gord_serves(s, OP_SOUP_ORDERED, dev != 0, &why)) return 0;
   srnn::WWave g;
   return dev && (srnn::gord_wave_serves(s, g) || srnn::gord_rnn_serves(s)) ? 2 : 1;
+}
+
+// the kernel family of a runtime shape's OP_TRAIN on the host (dev 0) / device (dev 1), with the knobs
+// in force: 0 not a valid shape, 1 a lane per particle (k_generic), 2 a wave kernel (k_rnn_wave,
+// k_ww_wave).  OP_RUN_MIXED always runs a lane per particle here; the caller picks the op sequence
+// where training has a wave kernel
+extern "C" int srnn_generic_train_form(const SrnnCfg* c, int dev) {
+  srnn::GShape s;
+  const char* why = "";
+  if (!srnn::make_gshape(*c, s, &why)) return 0;
+  SrnnArgs probe{};
+  probe.dev = dev;
+  srnn::WWave g;
+  return srnn::rw_serves(OP_TRAIN, s, probe) || srnn::ww_serves(OP_TRAIN, s, probe, g) ? 2 : 1;
 }
 
 // 1 when the runtime-shape engine serves `op` of this configuration on the host (dev 0) / device

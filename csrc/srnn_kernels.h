@@ -393,6 +393,62 @@ struct Item {
     if (a.cls) a.cls[i] = classify_w(w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, x);
   }
 
+  // ---------------------------------------------------------------- mixed run
+  // reference code/experiment.py:94-109 (MixedFixpointExperiment.run_net) and
+  // code/setups/mixed-self-fixpoints.py:81-86: one self-attack, then `epochs` self-train epochs,
+  // until the net is divergent or a fixpoint.  Step s takes the counters c = ctr + s * (epochs + 2)
+  // (apply), c + 1 .. c + epochs (train); the final classification ctr + steps * (epochs + 2) --
+  // the schedule of the op sequence classify / run_fixpoint(1) / train / classify, to which this
+  // is bitwise equal.  early_exit 1: every step is checked; 2: step 0 is not.  The weights stay in
+  // registers for the whole run; lanes leave the loop one by one (no wave-wide operation inside).
+  SRNN_HD static void run_mixed(const SrnnCfg& c, const SrnnArgs& a, int64_t i, float4* samp, uint8_t* perm) {
+    float w[P], nw[P];
+    load(rowp(a.W, i), w);
+    const uint64_t uid = uid_of(a, i);
+    ApplyCtx x = actx(a, c, uid, a.ctr, perm);
+    TrainCtx tc;
+    tc.lr = a.lr;
+    tc.rng = rng(a);
+    tc.uid = uid;
+    tc.ctr = a.ctr;
+    tc.samp = samp;
+    tc.perm = perm;
+    tc.shuffle = (a.flags & SRNN_F_SHUFFLE) != 0;
+    tc.stride = SAMP_STRIDE;
+    tc.aggregator = c.aggregator;
+    if (a.traj) store(rowp(a.traj, i), w);
+    const uint32_t stride = (uint32_t)a.epochs + 2u;
+    float loss = 0.f;
+    int s = 0;
+    for (; s < a.steps; ++s) {
+      const bool check = s > 0 || a.early_exit == 1;
+      if (check && is_diverged<P>(w)) break;
+      Net::apply(w, w, nw, x);
+      q(nw);
+      if (check && !is_diverged<P>(nw) && within_eps<P>(nw, w, a.eps)) break;  // is_fixpoint()
+      copy(w, nw);
+      tc.ctr = x.ctr + 1u;
+      if (a.epochs > 0) {
+        if constexpr (Net::KIND == 0) {
+          loss = Net::template train_epochs<true>(w, nw, a.epochs, tc);
+        } else {
+          for (int e = 0; e < a.epochs; ++e) {
+            copy(nw, w);  // (nw is free after the copy above: the epoch's frozen samples)
+            loss = Net::train_epoch(w, nw, tc);
+          }
+        }
+      }
+      q(w);  // the stored state: what OP_TRAIN's store rounds on a 16-bit table
+      x.ctr += stride;
+      if (a.traj) store(rowp(a.traj, (int64_t)(s + 1) * a.n + i), w);
+    }
+    if (s > 0) store(rowp(a.W, i), w);
+    if (a.nsteps) a.nsteps[i] = s;
+    x.ctr = a.ctr + (uint32_t)a.steps * stride;
+    if (a.cls) a.cls[i] = classify_w(w, a.eps, (a.flags & SRNN_F_FIX_SEC) != 0, x);
+    if (a.loss) a.loss[i] = loss;
+  }
+
   // ---------------------------------------------------------------- known-fixpoint variation
   // reference code/setups/known-fixpoint-variation.py:66-83
   SRNN_HD static void vary_run(const SrnnCfg& c, const SrnnArgs& a, int64_t i, float4*, uint8_t* perm) {
@@ -723,7 +779,7 @@ template <class Net, int OP, class S>
 __global__ __launch_bounds__(TB) void k_op(SrnnCfg c, SrnnArgs a) {
   using I = Item<Net, S>;
   constexpr int P = Net::P;
-  constexpr bool NEED_SAMP = (OP == OP_TRAIN || OP == OP_LEARN) && Net::KIND == 0;
+  constexpr bool NEED_SAMP = (OP == OP_TRAIN || OP == OP_LEARN || OP == OP_RUN_MIXED) && Net::KIND == 0;
   constexpr int SAMP = NEED_SAMP ? samp_slots<Net>() : 1;  // slot-major [P][TB]: lane fastest
   constexpr int PERM = (P + 4) & ~3;
   __shared__ float4 s_samp[TB * SAMP];
@@ -748,6 +804,7 @@ __global__ __launch_bounds__(TB) void k_op(SrnnCfg c, SrnnArgs a) {
     else if constexpr (OP == OP_PERTURB) I::perturb(c, a, i, samp, perm);
     else if constexpr (OP == OP_RESPAWN) I::respawn(a, i);
     else if constexpr (OP == OP_VARY_RUN) I::vary_run(c, a, i, samp, perm);
+    else if constexpr (OP == OP_RUN_MIXED) I::run_mixed(c, a, i, samp, perm);
   }
 }
 
@@ -1863,6 +1920,7 @@ int host_run(const SrnnCfg& c, const SrnnArgs& a) {
     else if constexpr (OP == OP_PERTURB) I::perturb(c, a, i, samp, perm);
     else if constexpr (OP == OP_RESPAWN) I::respawn(a, i);
     else if constexpr (OP == OP_VARY_RUN) I::vary_run(c, a, i, samp, perm);
+    else if constexpr (OP == OP_RUN_MIXED) I::run_mixed(c, a, i, samp, perm);
   });
   return 0;
 }
@@ -1964,6 +2022,7 @@ int run_net_op(int op, const SrnnCfg& c, const SrnnArgs& a) {
     case OP_SOUP_EVOLVE: return run_one<Net, OP_SOUP_EVOLVE, S>(c, a);
     case OP_RESPAWN: return run_one<Net, OP_RESPAWN, S>(c, a);
     case OP_VARY_RUN: return run_one<Net, OP_VARY_RUN, S>(c, a);
+    case OP_RUN_MIXED: return run_one<Net, OP_RUN_MIXED, S>(c, a);
     case OP_SOUP_GEN: return soup_gen<Net, S>(c, a);
     case OP_GEN_FINISH: return gen_finish<Net, S>(c, a);
     case OP_SOUP_SEQ: return soup_seq<Net, S>(c, a);

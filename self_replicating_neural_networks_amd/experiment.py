@@ -10,7 +10,8 @@ objects are produced, and ``from_dill`` reads reference files with a restricted
 unpickler that never executes code from the file.
 
 Population-scale extensions: ``FixpointExperiment.run_population`` runs the per-net
-``run_net`` loop for a whole population on the device in one kernel.
+``run_net`` loop for a whole population on the device in one kernel, and
+``MixedFixpointExperiment.run_population`` the mixed self-attack / self-train loop.
 """
 from __future__ import annotations
 
@@ -174,6 +175,35 @@ class MixedFixpointExperiment(FixpointExperiment):
             if run_id:
                 net.save_state()
         self.count(net)
+
+    # ------------------------------------------------------------------ population scale
+    def run_population(self, population, trains_per_application=100, step_limit=100, record=False, eps=None,
+                       collect_fixpoints=True) -> Dict[str, int]:
+        """``run_net`` for every particle of a ``Population`` in one fused launch (``Population.run_mixed``);
+        counters accumulate like repeated ``run_net`` calls.  ``record``: ``historical_particles[uid]``
+        is the init state and one state per performed step (no ``time``: the reference saves them bare)."""
+        eps = eps or 1e-4
+        cls, nsteps, _, traj = population.run_mixed(trains_per_application, step_limit, eps, check_first=True,
+                                                    record=bool(record))
+        c = np.bincount(cls.cpu().numpy().astype(np.int64), minlength=5)
+        for i, name in enumerate(CLASS_NAMES):
+            self.counters[name] += int(c[i])
+        if collect_fixpoints:
+            idx = torch.nonzero(cls == 2).flatten()
+            for row in population.W[idx, : population.spec.P].float().cpu().numpy():
+                self.interesting_fixpoints.append(population.spec.unflatten(row))
+        if record:
+            cname, P = population.spec.class_name, population.spec.P
+            dense, ns = traj.cpu().float().numpy(), nsteps.cpu().numpy()
+            for r, uid in enumerate(population.uid.cpu().tolist()):
+                states = [{"class": cname, "weights": dense[0, r, :P].copy(), "time": 0, "action": "init",
+                           "counterpart": None}]
+                for s in range(1, int(ns[r]) + 1):
+                    w = dense[s, r, :P]
+                    if np.all(np.isfinite(w)):
+                        states.append({"class": cname, "weights": w.copy()})
+                self.historical_particles[uid] = states
+        return {n: int(c[i]) for i, n in enumerate(CLASS_NAMES)}
 
 
 class SoupExperiment(Experiment):

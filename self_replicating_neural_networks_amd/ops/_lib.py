@@ -11,6 +11,7 @@ Field order of ``SrnnCfg``/``SrnnArgs`` mirrors ``csrc/srnn_abi.h``.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import subprocess
@@ -45,6 +46,7 @@ OP_SOUP_ORDERED = 22  # reference-order (sequential) generation, DAG-scheduled (
 OP_SOUP_ORDERED_SH = 23  # one phase of a sharded reference-order generation (csrc/srnn_ordered_sh.h)
 OP_ORD_PLAN = 24  # the plan of a reference-order generation (lists, versions, records, permutations)
 OP_ORD_CENSUS = 25  # the census of a reference-order generation's final rows into its block stats
+OP_RUN_MIXED = 26  # mixed run: self-attack + N self-train epochs per step until divergent / fixpoint
 ORDSH_PLAN, ORDSH_LEVEL, ORDSH_PACK, ORDSH_UNPACK, ORDSH_CLOSE, ORDSH_LINK = range(6)
 ORD_CTL_WORDS = 166   # o_ctl words of an ordered generation (csrc/srnn_ordered.h)
 ORD_MAXLW, ORD_ERRW = 17, 18
@@ -202,6 +204,10 @@ def lib():
         L.srnn_generic_ord_scratch_bytes.restype = ctypes.c_int64
         L.srnn_ord_run_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int]
         L.srnn_ord_run_form.restype = ctypes.c_int
+        L.srnn_train_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int]
+        L.srnn_train_form.restype = ctypes.c_int
+        L.srnn_mixed_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int, ctypes.c_int]
+        L.srnn_mixed_form.restype = ctypes.c_int
         L.srnn_big_fix_temp_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
         L.srnn_big_fix_temp_bytes.restype = ctypes.c_int64
         L.srnn_set_force_generic.argtypes = [ctypes.c_int]
@@ -359,10 +365,33 @@ def ord_run_form(spec, dev: bool = True, dtype_code: int = DTYPE_FP32):
     return {1: "lane", 2: "wave"}.get(r)
 
 
+def train_form(spec, device: bool = True, dtype: int = DTYPE_FP32):
+    """The kernel family that serves ``OP_TRAIN`` of this architecture on the device (``device=True``) or
+    the host, with the knobs in force: ``"lane"`` -- a lane per particle (the lane templates, the
+    runtime-shape lane engine), ``"wave"`` -- a wave or row kernel (wide Weightwise / Recurrent
+    runtime shapes, the big aggregating nets), ``None`` -- not a valid shape.  ``kernels.run_mixed``
+    runs the fused ``OP_RUN_MIXED`` on the lane form and the op sequence on the wave form."""
+    r = int(lib().srnn_train_form(ctypes.byref(make_cfg(spec, dtype)), 1 if device else 0))
+    return {1: "lane", 2: "wave"}.get(r)
+
+
+def mixed_form(spec, device: bool, trains: int, dtype: int = DTYPE_FP32):
+    """The form ``kernels.run_mixed`` takes for ``trains`` epochs per step: ``"fused"`` -- one
+    ``OP_RUN_MIXED`` launch, ``"ops"`` -- the op sequence on compacted tables (shapes whose training has
+    a wave / row kernel, and on the device long training steps of the lane shapes, where the measured
+    times say so: profiles/mixed_run.md), ``None`` -- not a valid shape."""
+    r = int(lib().srnn_mixed_form(ctypes.byref(make_cfg(spec, dtype)), 1 if device else 0, int(trains)))
+    return {1: "fused", 2: "ops"}.get(r)
+
+
 def big_fix_temp_bytes(spec, n: int, steps: int = 0, dense: bool = False) -> int:
     """``temp`` bytes of a run_fixpoint on the chunk-state kernels (csrc/srnn_bignet.h): the states and
     flags of ``n`` rows, plus -- ``dense`` -- the chunk-state trajectory a dense recording is expanded from."""
     return int(lib().srnn_big_fix_temp_bytes(int(spec.aggregates), int(n), int(steps), 1 if dense else 0))
+
+
+# successful srnn_run calls per op code (tests read which operator served a call)
+op_calls = collections.Counter()
 
 
 def run(op: int, spec, args: SrnnArgs, cfg: SrnnCfg = None, dtype: int = DTYPE_FP32) -> None:
@@ -372,6 +401,7 @@ def run(op: int, spec, args: SrnnArgs, cfg: SrnnCfg = None, dtype: int = DTYPE_F
     if r != 0:
         msg = L.srnn_last_error().decode(errors="replace")
         raise NativeLibraryError(f"srnn op {op} failed ({r}): {msg} [spec={spec}]")
+    op_calls[int(op)] += 1
 
 
 def last_error() -> str:

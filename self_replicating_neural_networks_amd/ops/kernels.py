@@ -307,3 +307,106 @@ def classify(spec, W: torch.Tensor, eps: float, with_sec: bool = True, uid=None,
     a.uid = _p(_uid(uid, n, W.device))
     _lib.run(_lib.OP_CLASSIFY, spec, a, dtype=dt)
     return cls, counts
+
+
+# -------------------------------------------------------------------------------- mixed runs
+# One self-attack followed by ``trains`` self-train epochs per step, until a net is divergent or a
+# fixpoint (reference code/experiment.py:94-109, code/setups/mixed-self-fixpoints.py:81-86).
+# Counter schedule (docs/semantics.md): step s applies at c = ctr + s * (trains + 2), trains at
+# c + 1 .. c + trains; the final classification is at ctr + steps * (trains + 2).
+def _mixed_outputs(spec, W, steps, record):
+    n = W.shape[0]
+    nsteps = torch.zeros(n, dtype=torch.int32, device=W.device)
+    loss = torch.zeros(n, dtype=torch.float32, device=W.device)
+    traj = torch.zeros((max(steps, 0) + 1, n, spec.PP), dtype=W.dtype, device=W.device) if record else None
+    return nsteps, loss, traj
+
+
+def _check_mixed(trains, steps):
+    trains, steps = int(trains), int(steps)
+    if trains < 0 or steps < 0:
+        raise ValueError(f"mixed run: trains and steps must be >= 0, got trains={trains} steps={steps}")
+    return trains, steps
+
+
+def run_mixed_fused(spec, W: torch.Tensor, trains: int, steps: int, eps: float, check_first: bool = True,
+                    with_sec: bool = True, lr: float = 0.01, shuffle: bool = True, record: bool = False, uid=None,
+                    seed=0, ctr=0):
+    """The mixed run as one ``OP_RUN_MIXED`` launch (a lane per particle, the weights in registers or
+    lane scratch across every self-attack and its epochs), in place.  See ``run_mixed``."""
+    dt = _check_table(spec, W)
+    trains, steps = _check_mixed(trains, steps)
+    n = W.shape[0]
+    cls = torch.empty(n, dtype=torch.int8, device=W.device)
+    nsteps, loss, traj = _mixed_outputs(spec, W, steps, record)
+    a = _base_args(W, seed, ctr)
+    a.n, a.steps, a.epochs, a.eps, a.lr = n, steps, trains, float(eps), float(lr)
+    a.early_exit = 1 if check_first else 2
+    a.flags = (_lib.FLAG_FIX_SEC if with_sec else 0) | (_lib.FLAG_SHUFFLE if shuffle else 0)
+    a.W, a.cls, a.nsteps, a.loss, a.traj = _p(W), _p(cls), _p(nsteps), _p(loss), _p(traj)
+    a.uid = _p(_uid(uid, n, W.device))
+    _lib.run(_lib.OP_RUN_MIXED, spec, a, dtype=dt)
+    return cls, nsteps, loss, traj
+
+
+def run_mixed_ops(spec, W: torch.Tensor, trains: int, steps: int, eps: float, check_first: bool = True,
+                  with_sec: bool = True, lr: float = 0.01, shuffle: bool = True, record: bool = False, uid=None,
+                  seed=0, ctr=0):
+    """The mixed run built from the existing operators on the same counter schedule: per step
+    ``classify(with_sec=False)`` and ``run_fixpoint(steps=1, early_exit=False)`` at ``c``, ``train(trains)``
+    at ``c + 1``; the final ``classify`` at ``ctr + steps * (trains + 2)``.  The rows still running are
+    gathered (with their uids, which key every random stream) into a compact table before each step
+    and scattered back after it, so stopped rows cost nothing.  Bitwise equal to ``run_mixed_fused``;
+    the form that keeps the wave / row training kernels of the shapes that have them."""
+    _check_table(spec, W)
+    trains, steps = _check_mixed(trains, steps)
+    n = W.shape[0]
+    nsteps, loss, traj = _mixed_outputs(spec, W, steps, record)
+    keys = _uid(uid, n, W.device)
+    if keys is None:  # without a uid column a row's streams are keyed by its index
+        keys = torch.arange(n, dtype=torch.int64, device=W.device)
+    if traj is not None:
+        traj[0] = W
+    idx = torch.arange(n, dtype=torch.int64, device=W.device)
+    for s in range(steps):
+        if idx.numel() == 0:
+            break
+        c = ctr + s * (trains + 2)
+        sub, su = W[idx].contiguous(), keys[idx].contiguous()
+        if s > 0 or check_first:
+            k, _ = classify(spec, sub, eps, with_sec=False, uid=su, seed=seed, ctr=c)
+            go = k == 4  # neither divergent nor a fixpoint
+            idx = idx[go]
+            if idx.numel() == 0:
+                break
+            sub, su = sub[go].contiguous(), su[go].contiguous()
+        run_fixpoint(spec, sub, 1, eps, early_exit=False, with_sec=False, uid=su, seed=seed, ctr=c)
+        if trains:
+            loss[idx] = train(spec, sub, trains, lr, shuffle, uid=su, seed=seed, ctr=c + 1)
+        W[idx] = sub
+        nsteps[idx] += 1
+        if traj is not None:
+            traj[s + 1, idx] = sub
+    cls, _ = classify(spec, W, eps, with_sec, uid=keys, seed=seed, ctr=ctr + steps * (trains + 2))
+    return cls, nsteps, loss, traj
+
+
+def run_mixed(spec, W: torch.Tensor, trains: int, steps: int, eps: float, check_first: bool = True,
+              with_sec: bool = True, lr: float = 0.01, shuffle: bool = True, record: bool = False, uid=None,
+              seed=0, ctr=0):
+    """Per-row ``MixedFixpointExperiment.run_net`` (code/experiment.py:94-109), in place: up to ``steps``
+    times one self-attack and ``trains`` self-train epochs, a row stopping once it is divergent or a
+    fixpoint.  ``check_first=False`` leaves step 0 unchecked (code/setups/mixed-self-fixpoints.py:81-86).
+
+    Returns (class int8[N], steps int32[N], last epoch's loss float32[N] -- 0 where no epoch ran,
+    trajectory [(steps+1), N, PP] with ``record`` -- row 0 the input, zero rows past a particle's last
+    step -- else None).
+
+    The form follows the shape (``_lib.mixed_form``): where ``OP_TRAIN`` runs a lane per particle
+    (``_lib.train_form``) the whole run is one fused launch; where it has a wave or row kernel the op
+    sequence keeps that kernel.  On the device the lane shapes also take the op sequence from a
+    measured number of epochs per step on (long training on the few rows still running: only the op
+    sequence compacts them).  Both forms give the same bits."""
+    form = _lib.mixed_form(spec, W.device.type == "cuda", _check_mixed(trains, steps)[0], dtype_code(W.dtype))
+    f = run_mixed_ops if form == "ops" else run_mixed_fused
+    return f(spec, W, trains, steps, eps, check_first, with_sec, lr, shuffle, record, uid, seed, ctr)

@@ -125,6 +125,15 @@ class Population:
         return K.run_fixpoint(self.spec, self.W, steps, eps, early_exit, with_sec, record, uid=self.uid,
                               seed=self.seed, ctr=self._next_ctr(steps + 2))
 
+    def run_mixed(self, trains: int, steps: int = 100, eps: float = 1e-4, check_first: bool = True, record=False,
+                  with_sec: bool = True, shuffle: bool = True):
+        """Mixed run of every particle (``K.run_mixed``): up to ``steps`` times one self-attack and
+        ``trains`` self-train epochs, a particle stopping once it is divergent or a fixpoint.
+        Returns (class, steps, loss, trajectory or None)."""
+        trains, steps = int(trains), int(steps)
+        return K.run_mixed(self.spec, self.W, trains, steps, eps, check_first, with_sec, self.lr, shuffle, record,
+                           uid=self.uid, seed=self.seed, ctr=self._next_ctr(steps * (trains + 2) + 1))
+
     def classify(self, eps: float = 1e-4, with_sec: bool = True):
         return K.classify(self.spec, self.W, eps, with_sec, uid=self.uid, seed=self.seed, ctr=self._next_ctr())
 

@@ -258,18 +258,9 @@ def mixed_self_fixpoints(trials=20, selfattacks=4, trains=None, epsilon=1e-4, de
             xs, ys = [], []
             for t in trains:
                 pop = Population(spec, trials, device=device, seed=_seed(seed) + 1000 * k + t)
-                active = torch.ones(trials, dtype=torch.bool, device=pop.device)
-                for _ in range(selfattacks):
-                    before = pop.W.clone()
-                    pop.self_apply(1)
-                    if t:
-                        pop.train(t)
-                    pop.W.copy_(torch.where(active[:, None], pop.W, before))
-                    cls, _ = pop.classify(epsilon, with_sec=False)
-                    active &= ~((cls == 0) | (cls == 1) | (cls == 2))
-                    if not bool(active.any()):
-                        break
-                c = pop.count(epsilon)
+                # one launch: step 0 unchecked, then a net stops once it is divergent or a fixpoint
+                cls, _, _, _ = pop.run_mixed(t, selfattacks, epsilon, check_first=False)
+                c = counts_dict(np.bincount(cls.cpu().numpy().astype(np.int64), minlength=5))
                 xs.append(t)
                 ys.append(float(c["fix_zero"] + c["fix_other"]) / float(trials))
             all_names.append(ref_name(spec))

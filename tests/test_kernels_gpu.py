@@ -10,23 +10,12 @@ from self_replicating_neural_networks_amd.ops import kernels as K
 from self_replicating_neural_networks_amd.oracle import core as O
 from self_replicating_neural_networks_amd.soup_engine import SoupEngine
 
+from rel_error import rel as _rel  # rows non-finite in the reference only are left out; see the module
+
 pytestmark = pytest.mark.gpu
 
 SPECS = [ArchSpec.weightwise(2, 2), ArchSpec.weightwise(4, 3), ArchSpec.aggregating(4, 2, 2),
          ArchSpec.aggregating(4, 2, 2, shuffler="random"), ArchSpec.recurrent(2, 2), ArchSpec.fft(4, 2, 2)]
-
-
-def _rel(a, b):
-    """max over rows of |a-b| / (row scale of b): robust to cancellation in single entries."""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    if a.ndim == 1:
-        a, b = a[:, None], b[:, None]
-    ok = np.all(np.isfinite(a), axis=1) & np.all(np.isfinite(b), axis=1)
-    if not ok.any():
-        return 0.0
-    a, b = a[ok], b[ok]
-    scale = np.max(np.abs(b), axis=1, keepdims=True) + 1e-6
-    return float(np.max(np.abs(a - b) / scale))
 
 
 @pytest.mark.parametrize("spec", SPECS, ids=lambda s: f"{s.kind}-{s.width}-{s.depth}-{s.shuffler}")
@@ -65,21 +54,37 @@ def test_init_apply_train_classify_vs_oracle(cuda, spec):
     assert int(counts.sum()) == n
 
 
-@pytest.mark.parametrize("spec", SPECS[:3] + SPECS[4:5], ids=lambda s: f"{s.kind}-{s.width}-{s.depth}")
-def test_device_matches_host_path(cuda, spec):
-    """Same C++ per-particle code on CPU threads and on the GPU."""
+def _device_matches_host_path(cuda, spec, scale):
+    """Same C++ per-particle code on CPU threads and on the GPU.  From the init rows 27 % of the
+    RNN(2,2) rows are finite after three epochs on the host (every row of the other nets); from the
+    half-scale rows every row of every net is.  At least 90 % must be compared everywhere but for
+    RNN(2,2) at init scale."""
     n, seed = 1000, 5
     uid = torch.arange(n, dtype=torch.int64)
     Wc = torch.zeros(n, spec.PP)
     K.init_rows(spec, Wc, uid, seed)
+    Wc *= scale
     Wg = Wc.to(cuda)
     K.train(spec, Wc, epochs=3, uid=uid, seed=seed)
     K.train(spec, Wg, epochs=3, uid=uid.to(cuda), seed=seed)
-    # same C++ code; fma contraction differs host/device: BPTT amplifies the last ulps
-    assert _rel(Wg.cpu().numpy(), Wc.numpy()) < (5e-3 if spec.kind == "recurrent" else 1e-4)
+    # the same C++ code with the same contraction on both sides (-ffp-contract=on, host -mfma).  This test
+    # keeps its tolerance; tests/test_exact_oracle.py and tests/test_exact_families_gpu.py hold the host and
+    # the device to the exact oracle at zero tolerance.
+    share = 0.0 if spec.kind == "recurrent" and scale == 1.0 else 0.9
+    assert _rel(Wg.cpu().numpy(), Wc.numpy(), min_share=share) < (5e-3 if spec.kind == "recurrent" else 1e-4)
     cc, _ = K.run_fixpoint(spec, Wc, 5, 1e-4)[:2]
     cg, _ = K.run_fixpoint(spec, Wg, 5, 1e-4)[:2]
     assert (cc.numpy() == cg.cpu().numpy()).mean() > 0.99
+
+
+@pytest.mark.parametrize("spec", SPECS[:3] + SPECS[4:5], ids=lambda s: f"{s.kind}-{s.width}-{s.depth}")
+def test_device_matches_host_path(cuda, spec):
+    _device_matches_host_path(cuda, spec, 1.0)
+
+
+@pytest.mark.parametrize("spec", SPECS[:3] + SPECS[4:5], ids=lambda s: f"{s.kind}-{s.width}-{s.depth}")
+def test_device_matches_host_path_from_half_scale_rows(cuda, spec):
+    _device_matches_host_path(cuda, spec, 0.5)
 
 
 def test_run_fixpoint_statistics_weightwise(cuda):
@@ -108,7 +113,7 @@ def test_soup_engine_gpu_vs_oracle(cuda):
     W1, act, cp, loss, resp = O.soup_generation_sync(spec, W0, uids, 1, 7, params)
     keep = resp == 0
     # a generation = attacks + learn_from + 3 epochs of SGD (~60 dependent steps per particle)
-    assert _rel(e.local_rows()[:, :spec.P].cpu().numpy()[keep], W1[keep]) < 1e-5
+    assert _rel(e.local_rows()[:, :spec.P].cpu().numpy()[keep], W1[keep], min_share=0.9) < 1e-5
     assert (e.action.cpu().numpy() == act).all()
     assert (e.counterpart.cpu().numpy() == cp).all()
     assert (e.respawn.cpu().numpy() == resp).mean() > 0.999
@@ -130,15 +135,20 @@ def test_soup_graph_replay_matches_eager(cuda):
 BIG = [ArchSpec.aggregating(4, 10, 3), ArchSpec.aggregating(4, 8, 2, aggregator="max")]
 
 
-@pytest.mark.parametrize("spec", BIG, ids=lambda s: f"agg-{s.aggregates}-{s.width}-{s.depth}-{s.aggregator}")
-def test_wave_per_particle_aggregating_vs_oracle(cuda, spec):
-    """Aggregating(4, 10, 3) (P = 280, north-star config) runs wave-per-particle."""
+def _wave_per_particle_aggregating_vs_oracle(cuda, spec, scale):
+    """Aggregating(4, 10, 3) (P = 280, north-star config) runs wave-per-particle.  Five
+    self-applications of Aggregating(4, 8, 2, max) from its init rows leave 44 % of the oracle's rows
+    below 1e30; from the half-scale rows every row of both nets, and at least 90 % must be compared."""
     n, seed = 3000, 21
+    share = 0.9 if scale != 1.0 else 0.0
     uid = torch.arange(n, dtype=torch.int64, device=cuda)
     W = torch.zeros(n, spec.PP, device=cuda)
     K.init_rows(spec, W, uid, seed)
     ow = O.init(spec, uid.cpu().numpy(), seed)
     assert _rel(W[:, :spec.P].cpu().numpy(), ow) < 1e-5
+    if scale != 1.0:
+        W *= scale
+        ow = W[:, :spec.P].cpu().numpy().copy()
     out = torch.zeros_like(W)
     idx_f = torch.roll(torch.arange(n, device=cuda), 1).contiguous()
     K.apply(spec, W, out, idx_f=idx_f)
@@ -152,7 +162,7 @@ def test_wave_per_particle_aggregating_vs_oracle(cuda, spec):
         for _ in range(5):
             w = O.apply(spec, w, w)
     # five chained degree-(D+1) polynomial maps amplify fma-order ulps: compare loosely
-    assert _rel(W5[:, :spec.P].cpu().numpy(), w) < 1e-2
+    assert _rel(W5[:, :spec.P].cpu().numpy(), w, min_share=share) < 1e-2
     assert (cls.cpu().numpy() == O.classify(spec, w, 1e-4)).mean() > 0.99
     c2, counts = K.classify(spec, W, 1e-4)
     assert (c2.cpu().numpy() == O.classify(spec, ow, 1e-4)).mean() > 0.99 and int(counts.sum()) == n
@@ -161,8 +171,18 @@ def test_wave_per_particle_aggregating_vs_oracle(cuda, spec):
     tw = ow.copy()
     for _ in range(3):
         tw, tl = O.train_epoch(spec, tw, tw, 0.01, False)
-    assert _rel(W2[:, :spec.P].cpu().numpy(), tw) < 1e-4
-    assert _rel(loss.cpu().numpy(), tl) < 1e-4
+    assert _rel(W2[:, :spec.P].cpu().numpy(), tw, min_share=0.9) < 1e-4
+    assert _rel(loss.cpu().numpy(), tl, min_share=0.9) < 1e-4
+
+
+@pytest.mark.parametrize("spec", BIG, ids=lambda s: f"agg-{s.aggregates}-{s.width}-{s.depth}-{s.aggregator}")
+def test_wave_per_particle_aggregating_vs_oracle(cuda, spec):
+    _wave_per_particle_aggregating_vs_oracle(cuda, spec, 1.0)
+
+
+@pytest.mark.parametrize("spec", BIG, ids=lambda s: f"agg-{s.aggregates}-{s.width}-{s.depth}-{s.aggregator}")
+def test_wave_per_particle_aggregating_vs_oracle_from_half_scale_rows(cuda, spec):
+    _wave_per_particle_aggregating_vs_oracle(cuda, spec, 0.5)
 
 
 def test_big_aggregating_applying_statistics(cuda):
@@ -201,7 +221,7 @@ def test_mfma_weightwise_vs_oracle(cuda, spec):
     with np.errstate(all="ignore"):
         for _ in range(3):
             w = O.apply(spec, w, w)
-    assert _rel(W3[:, :spec.P].cpu().numpy(), w) < 1e-2
+    assert _rel(W3[:, :spec.P].cpu().numpy(), w, min_share=0.9) < 1e-2
     assert (cls.cpu().numpy() == O.classify(spec, w, 1e-4)).mean() > 0.98
     c0, counts = K.classify(spec, W, 1e-4)
     assert (c0.cpu().numpy() == O.classify(spec, ow, 1e-4)).mean() > 0.99 and int(counts.sum()) == n
@@ -381,9 +401,9 @@ def test_big_aggregating_row_kernels_match_wave_kernels(cuda, aggregator, monkey
     assert (a[1] == b[1]).float().mean() > 0.999
     assert torch.equal(a[2], b[2]) or (a[2] - b[2]).abs().sum() <= 2
     for i in (3, 5):
-        assert _rel(a[i][:, :spec.P].cpu().numpy(), b[i][:, :spec.P].cpu().numpy()) < 1e-5
+        assert _rel(a[i][:, :spec.P].cpu().numpy(), b[i][:, :spec.P].cpu().numpy(), min_share=0.9) < 1e-5
     for i in (4, 6):
-        assert _rel(a[i].cpu().numpy(), b[i].cpu().numpy()) < 1e-4
+        assert _rel(a[i].cpu().numpy(), b[i].cpu().numpy(), min_share=0.9) < 1e-4
     assert torch.equal(a[7], b[7]) and torch.equal(a[8], b[8]) and torch.equal(a[9], b[9])  # run_fixpoint
 
 

@@ -9,6 +9,8 @@ from self_replicating_neural_networks_amd.ops import _lib
 from self_replicating_neural_networks_amd.ops import kernels as K
 from self_replicating_neural_networks_amd.oracle import core as O
 
+from rel_error import rel as rowrel  # rows non-finite in the reference only are left out; see the module
+
 SPECS = [ArchSpec.weightwise(2, 2), ArchSpec.weightwise(1, 1), ArchSpec.weightwise(4, 3), ArchSpec.weightwise(8, 2),
          ArchSpec.aggregating(4, 2, 2), ArchSpec.aggregating(4, 2, 2, aggregator="max"),
          ArchSpec.aggregating(4, 2, 2, aggregator="max_ref"), ArchSpec.aggregating(4, 2, 2, shuffler="random"),
@@ -20,13 +22,6 @@ SPECS = [ArchSpec.weightwise(2, 2), ArchSpec.weightwise(1, 1), ArchSpec.weightwi
          ArchSpec.aggregating(4, 10, 2), ArchSpec.aggregating(4, 10, 3), ArchSpec.aggregating(5, 3, 2, shuffler="random"),
          ArchSpec.recurrent(3, 2), ArchSpec.recurrent(5, 1), ArchSpec.fft(3, 2, 2)]
 IDS = [f"{s.kind}-{s.aggregates}-{s.width}-{s.depth}-{s.aggregator}-{s.shuffler}" for s in SPECS]
-
-
-def rowrel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    ok = np.all(np.isfinite(a), 1) & np.all(np.isfinite(b), 1)
-    a, b = a[ok], b[ok]
-    return float(np.max(np.abs(a - b) / (np.max(np.abs(b), 1, keepdims=True) + 1e-6))) if len(a) else 0.0
 
 
 @pytest.fixture(params=SPECS, ids=IDS)
@@ -115,13 +110,24 @@ def test_classify_matches_oracle(spec):
 
 
 def test_run_fixpoint_matches_oracle_short():
+    _run_fixpoint_matches_oracle_short(1.0)
+
+
+def test_run_fixpoint_matches_oracle_short_from_half_scale_rows():
+    _run_fixpoint_matches_oracle_short(0.5)
+
+
+def _run_fixpoint_matches_oracle_short(scale):
+    """five steps from the init rows leave 80 % of the oracle's rows finite, from the half-scale
+    rows every row: there at least 90 % must be compared"""
     spec = ArchSpec.weightwise(2, 2)
     W, uid = _pop(spec, 500)
+    W *= scale
     ow = W[:, :spec.P].numpy().copy()
     cls, nsteps, _ = K.run_fixpoint(spec, W, 5, 1e-4, early_exit=True)
     w5, n5, c5 = O.run_fixpoint(spec, ow, 5, 1e-4, early_exit=True)
     assert (nsteps.numpy() == n5).mean() > 0.99
-    assert rowrel(W[:, :spec.P].numpy(), w5) < 1e-3
+    assert rowrel(W[:, :spec.P].numpy(), w5, min_share=0.9 if scale != 1.0 else 0.0) < 1e-3
 
 
 def test_perturb_matches_oracle():

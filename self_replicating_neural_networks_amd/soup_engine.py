@@ -43,13 +43,14 @@ exact reference order.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
-import os
 from typing import Dict, Optional
 
 import torch
 
+from . import soup_graphs
 from .arch import ArchSpec
 from .config import ExecConfig
 from .ops import _lib
@@ -80,14 +81,6 @@ ORD_ERR_EMULATED = 32
 
 def describe_ordered_error(bits: int) -> str:
     return "; ".join(f"{b}: {msg}" for b, msg in ORD_ERRORS.items() if bits & b) or f"error bits {bits}"
-
-
-class _nullcontext:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 
 def _p(t):
@@ -268,6 +261,22 @@ def plan_population(spec: ArchSpec, dtype=torch.float32, exchange: str = "alltoa
 class SoupEngine:
     """Population-sharded soup on one device per rank."""
 
+    # the host fields a generation, flush, finish or graph replay advances (_host_state)
+    HOST_STATE = ("_p", "time", "_pending", "_lists_ready", "_pending_fin", "_census_due", "_census_log_rows",
+                  "_fin_flags", "_primed")
+    # every device tensor (or list of them) a generation reads or writes: saved, restored and
+    # compared by the graph validation (_state); None on the engine kinds without it
+    DEVICE_STATE = ("_bufs", "uid", "next_uid", "_gen_ring", "heads", "nexts", "ballots", "rowflags", "action",
+                    "counterpart", "loss", "respawn", "counts", "census", "err", "full", "stats_all", "_blockstat",
+                    "_done", "_bs_ring", "x_dep", "x_rlist", "x_rcount", "x_rslot", "x_satt", "x_cno", "x_crq",
+                    "x_srep", "x_nsrep", "x_part", "x_ctl", "x_bstat", "x_hpre", "x_hgrp", "sendbuf", "recvbuf",
+                    "_abuf", "_osrc", "_olist", "_octl", "_ptab", "_osrc1", "_olist1", "_octl1", "_ptab1", "_osync",
+                    "_fw", "_sh_heads", "_sh_nexts", "_sh_cnt", "_sh_send", "_sh_recv", "_census_log")
+    # ... of which a replay must reproduce the eager generations bitwise (the others -- exchange-buffer
+    # row order, the attack lists' link order -- follow atomics and legitimately differ between runs)
+    COMPARED_STATE = ("_bufs", "uid", "next_uid", "_gen_ring", "counts", "census", "loss", "respawn", "action",
+                      "counterpart", "err")
+
     def __init__(self, spec: ArchSpec, n_total: int, params: Dict, device="cpu", seed: int = 0,
                  lr: float = 0.01, shuffle: bool = True, dist: Optional[Dist] = None, weights=None,
                  dtype: torch.dtype = torch.float32, exchange: str = "alltoall", local_weights=None,
@@ -368,12 +377,23 @@ class SoupEngine:
         self.trajectory = None      # sampled TrajectoryRecorder (large soups)
         self.metrics = None         # MetricsWriter (JSONL per-generation metrics)
         self._metrics_uid = None
-        self._graphs = None
-        self._chunk = None          # (graph of G generations, start parity, G): the largest
-        self._chunks = []           # every captured multi-generation graph, largest first
+        self._graphs = None         # the single-generation graphs by parity (soup_graphs)
+        self._chunks = []           # every captured multi-generation graph (soup_graphs.Chunk), largest first
+        self._conc = None           # whether the side stream runs beside the current one (probed once)
         self._arg_cache = {}
         self._pending = False       # sharded: uids of the last generation's newborns not yet assigned
+        self._pending_fin = 0       # batched finish: generations whose finish is still due
+        self._fin_flags = 0         # ... the flags of the last of them
+        self._primed = False        # sharded all-to-all: the first exchange has run (_x2_prime)
         self.overlap = False        # sharded all-to-all: the exchange runs beside the local evolve
+        # device state of the other engine kinds (DEVICE_STATE) and buffers allocated on first use
+        self.full = self.stats_all = self._blockstat = self._done = self._bs_ring = self.sendbuf = self.recvbuf = None
+        self.x_dep = self.x_rlist = self.x_rcount = self.x_rslot = self.x_satt = self.x_cno = self.x_crq = None
+        self.x_srep = self.x_nsrep = self.x_part = self.x_ctl = self.x_bstat = self.x_hpre = self.x_hgrp = None
+        self._abuf = self._osrc = self._olist = self._octl = self._osrc1 = self._olist1 = self._octl1 = None
+        self._fw = self._sh_heads = self._sh_nexts = self._sh_cnt = self._sh_send = self._sh_recv = None
+        self._ptab = self._ptab1 = self._uid_tmp = self._sh_key = self._sh_one = self._otrace = None
+        self._otrace_slots = 2
         if self.x2:
             self._init_x2(n_links)
         else:
@@ -384,7 +404,7 @@ class SoupEngine:
         self._ord_side = None       # ... on this side stream (device, mode "stream")
         self._ord_mode = "off"      # ... by the run launch ("kernel") or the side stream ("stream")
         self._ord_census_side = False  # ... with the census of each generation beside the next one
-        self._census_due = None
+        self._census_due = None     # ... the block stats of a generation whose census is still to run
         self._ord_decouple = False  # ... multi-generation graphs as two counter-ordered graphs (SRNN_F_ORD_SYNC)
         self._osync = None
         self._sync = False
@@ -430,7 +450,6 @@ class SoupEngine:
         self._batch = _finish_batch(nb, self._chunk_sizes())
         # (+ 8 bytes per generation: its newborn count, accumulated by the generation waves)
         self._bs_ring = torch.zeros((self._batch, nb * 8 + 2), **i32) if fm == "batch" else None
-        self._pending_fin = 0  # batch mode: generations whose finish is still due
         if self.dist.enabled:  # all-gather exchange
             self.full = torch.zeros((self.n_total, self.spec.PP), dtype=self.dtype, device=dev)
             self.stats_all = torch.zeros(self.dist.world * 6, dtype=torch.int64, device=dev)
@@ -469,7 +488,7 @@ class SoupEngine:
         # (reference order: the pending records' rows and the critical roots' rows, csrc k_ord_ptab)
         rows = 2 * _lib.ord_rec_total(self.n) if self.order == "sequential" else self.n
         name = "_ptab1" if q else "_ptab"
-        t = getattr(self, name, None)
+        t = getattr(self, name)
         if t is None or t.numel() < rows * E:
             t = torch.zeros(rows * E, dtype=torch.int64, device=self.device)
             setattr(self, name, t)
@@ -525,8 +544,6 @@ class SoupEngine:
         mode = self.execution.ord_pipeline
         self._ord_pipe = not sharded and mode != "off"
         self._ord_mode = mode if self._ord_pipe else "off"
-        self._osrc1 = self._olist1 = self._octl1 = None
-        self._ord_side = None
         if self._ord_pipe:
             self._osrc1 = torch.zeros_like(self._osrc)
             self._olist1 = torch.zeros_like(self._olist)
@@ -547,7 +564,6 @@ class SoupEngine:
         # final rows, ballots and counter
         self._ord_census_side = (self._ord_side is not None and bool(self.execution.ord_census_side) and
                                  _lib.supports(self.spec, _lib.OP_ORD_CENSUS, True, self.dtype_code))
-        self._census_due = None  # the block stats of a generation whose census is still to run
         self._rec_rows = None  # recording: every particle's state before any respawn
 
     def _ord_set(self, q: int):
@@ -600,7 +616,7 @@ class SoupEngine:
         claim, acquire, record and level reads) -- mean / max per level.  ``critical``: the chain
         that ends last, turn by turn (start, end, hand-off before it)."""
         n = self.n
-        S = getattr(self, "_otrace_slots", 2)
+        S = self._otrace_slots
         raw = self._otrace.view(-1, S).cpu().double()[:n]
         t = raw[:, [0, 7 if S >= 8 else S - 1]]
         osrc, _, octl = self._ord_set(self._ord_last())
@@ -713,9 +729,6 @@ class SoupEngine:
         self.schedule = self.execution.x2_schedule
         # the lane kernels evolve both kinds of slot in one launch (bignet / runtime-shape: two)
         self._x2_both = not bignet and not _lib.is_generic(self.spec, _lib.OP_SOUP_EVOLVE, self.dtype_code)
-        # single-launch generations: pack leaves, per 64-row block, how many remote-dependent slots
-        # come before it (the launch's lanes on those slots take the remote list's entries)
-        self.x_hpre = self.x_hgrp = None
         p = self.params
         cr, cn, cq = x2_capacities(self.n_total, R, float(p.get("attacking_rate", 0.1)),
                                    float(p.get("learn_from_rate", 0.1)), int(p.get("segment", 0) or 0))
@@ -750,6 +763,8 @@ class SoupEngine:
         self.x_nsrep = torch.zeros(R, **i32)
         self.x_part = torch.zeros(self.x_groups * 6, **i64)
         if self.schedule == "serial" and self._x2_both:
+            # single-launch generations: pack leaves, per 64-row block, how many remote-dependent slots
+            # come before it (the launch's lanes on those slots take the remote list's entries)
             self.x_hpre = torch.zeros(nb, **i32)
             self.x_hgrp = torch.zeros(self.x_groups, **i32)
         self.x_ctl = torch.zeros(8, **i32)
@@ -758,7 +773,6 @@ class SoupEngine:
         self.sendbuf = torch.full((R * self.x_blk,), 255, dtype=torch.uint8, device=dev)
         self.recvbuf = torch.zeros(R * self.x_blk, dtype=torch.uint8, device=dev)
         self.stats_all = torch.zeros(R * 6, **i64)
-        self._primed = False
         self._xs = torch.cuda.Stream(dev) if dev.type == "cuda" else None  # local evolve
         self._xp = torch.cuda.Stream(dev) if dev.type == "cuda" else None  # post
         self.overlap = self._xs is not None and self.schedule == "overlap"
@@ -826,10 +840,8 @@ class SoupEngine:
         return self.stats and self.spec.shuffler == "none"
 
     def _cache_key(self, *extra):
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
-        return (self._p, stream, tuple(sorted((k, str(v)) for k, v in self.params.items())), self.stats,
-                self.stats_with_sec, self.lr, self.shuffle, self._pending_fin if not self.x2 else 0,
-                self._sync) + extra
+        return (self._p, self._stream_key(), tuple(sorted((k, str(v)) for k, v in self.params.items())), self.stats,
+                self.stats_with_sec, self.lr, self.shuffle, self._pending_fin, self._sync) + extra
 
     # ------------------------------------------------------------------ single rank / all-gather
     def _gen_args(self):
@@ -900,7 +912,7 @@ class SoupEngine:
                     fa.ptab_next = _p(self._perm_table(1 - q))
                     fa.o_plan_groups = self.plan_groups(self.n)
                 fa.o_levels = self.order_levels
-                fa.o_trace = _p(getattr(self, "_otrace", None))
+                fa.o_trace = _p(self._otrace)
             ca = fa
         self._arg_cache[key] = (a, ca, a.flags)
         return self._arg_cache[key]
@@ -990,7 +1002,7 @@ class SoupEngine:
                 if self._ord_side is not None:
                     side, main = self._ord_side, torch.cuda.current_stream(self.device)
                     side.wait_stream(main)
-                with torch.cuda.stream(side) if side is not None else _nullcontext():
+                with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
                     self._run_census_due()
                 _lib.run(_lib.OP_ORD_PLAN, spec, self._plan_args(True), cfg)
         elif not self._lists_ready:
@@ -1146,7 +1158,7 @@ class SoupEngine:
         B = self._SH_LEVEL_BINS
         lv = self._osrc[:4 * N].view(N, 4)[:, 3]
         if N <= (1 << 24):
-            if getattr(self, "_sh_key", None) is None or self._sh_key.numel() != N:
+            if self._sh_key is None or self._sh_key.numel() != N:
                 k = torch.arange(N, dtype=torch.int64, device=self.device)
                 self._sh_key = ((k + 1) * R - 1) // N * B
                 self._sh_one = torch.ones(N, dtype=torch.int64, device=self.device)
@@ -1203,10 +1215,17 @@ class SoupEngine:
 
     def _join_side(self):
         """Run any census and batched finish still due (uids, census, next_uid are final after this)."""
-        if self._census_due is not None:
-            self._run_census_due()  # (on the main stream: it reads the rows the close just wrote)
-        if not self.x2 and self._pending_fin:
+        self._run_census_due()  # (on the main stream: it reads the rows the close just wrote)
+        if self._pending_fin:
             self._finish_pending()
+
+    def _host_state(self):
+        """Snapshot of the HOST_STATE fields (graph capture and validation put it back)."""
+        return tuple(getattr(self, k) for k in self.HOST_STATE)
+
+    def _set_host_state(self, st):
+        for k, v in zip(self.HOST_STATE, st):
+            setattr(self, k, v)
 
     # ------------------------------------------------------------------ sharded all-to-all (X2)
     def _x2_base(self, p: int, stream=None) -> _lib.SrnnArgs:
@@ -1408,7 +1427,7 @@ class SoupEngine:
                 # the grid-wide assignment's scratch (csrc uid_temp_bytes: a count per 4096-row
                 # chunk + this rank's first uid); allocated once, outside graph captures
                 nb = (-(-self.n // 4096) * 4 + 7) // 8 * 8 + 8
-                t = getattr(self, "_uid_tmp", None)
+                t = self._uid_tmp
                 if t is None or t.numel() * 8 < nb:
                     self._uid_tmp = t = torch.zeros(nb // 8, dtype=torch.int64, device=self.device)
                 ua = self._args()
@@ -1488,12 +1507,11 @@ class SoupEngine:
         if not on:
             self._census_log, self._census_log_rows = None, 0
             return
-        if self.dist.enabled or getattr(self, "finish_mode", None) != "batch":
+        if self.dist.enabled or self.finish_mode != "batch":
             raise ValueError("census_log needs a single-rank engine with finish_mode='batch' (a GPU soup of an "
                              "instantiated shape)")
-        if self._census_log is None:
-            self._census_log = torch.zeros((self._batch, 6), dtype=torch.int64, device=self.device)
-            self._census_log_rows = 0
+        self._census_log = torch.zeros((self._batch, 6), dtype=torch.int64, device=self.device)
+        self._census_log_rows = 0
 
     def census_history(self) -> torch.Tensor:
         """``census_log``: rows ``[divergent, fix_zero, fix_other, fix_sec, other, respawns]`` of the
@@ -1507,21 +1525,18 @@ class SoupEngine:
         left = int(iterations)
         while left > 0:
             # the largest captured multi-generation graph that fits what is left
-            ch = next((c for c in self._chunks if c[2] <= left and c[1] == self._p), None)
+            ch = next((c for c in self._chunks if c.gens <= left and c.parity == self._p), None)
             if (ch is not None and not (record and self.recorder is not None)
                     and self.trajectory is None and self.metrics is None):
                 # G generations in one graph launch (no inter-graph gaps)
                 self._join_side()
-                self._replay_chunk(ch)
-                # (the chunk's finish launches, as captured: one per _batch generations and one at its end)
-                self._census_log_rows = (ch[2] - 1) % self._batch + 1 if self._census_log is not None else 0
-                self.time += ch[2]
-                left -= ch[2]
-                self._pending = self.dist.enabled
+                soup_graphs.replay_chunk(self, ch)
+                self._replayed(ch.gens)
+                left -= ch.gens
                 continue
             left -= 1
-            self.time += 1
             if record and self.recorder is not None:
+                self.time += 1
                 self._join_side()
                 slot_uid = self.global_uids()  # uid of every slot at generation start
                 self._generation(record=True)
@@ -1530,10 +1545,9 @@ class SoupEngine:
             elif self._graphs is not None:
                 self._join_side()
                 self._graphs[self._p].replay()
-                self._census_log_rows = 1 if self._census_log is not None else 0
-                self._p = 1 - self._p
-                self._pending = self.dist.enabled
+                self._replayed(1)
             else:
+                self.time += 1
                 self._generation()
             self._hooks()
         self._join_side()
@@ -1541,6 +1555,14 @@ class SoupEngine:
         if self.dist.native is not None:
             self.dist.native.check()  # RCCL asynchronous errors (peer failure) surface here
         return self
+
+    def _replayed(self, gens: int):
+        """The host state after a graph replay of ``gens`` generations (its finish launches, as
+        captured: one per _batch generations and one at its end)."""
+        self.time += gens
+        self._census_log_rows = (gens - 1) % self._batch + 1 if self._census_log is not None else 0
+        self._p ^= gens & 1
+        self._pending = self.dist.enabled
 
     def _hooks(self):
         """Per-generation observers (host work only when one is due)."""
@@ -1580,23 +1602,11 @@ class SoupEngine:
         self.dist.all_gather_rows(out, self.uid, self.n_total)
         return out.cpu().numpy()
 
-    # ------------------------------------------------------------------ HIP graphs
-    def _state(self):
-        """Every device tensor a generation reads or writes (graph validation)."""
-        names = ["_bufs", "uid", "next_uid", "_gen_ring", "heads", "nexts", "ballots", "rowflags", "action",
-                 "counterpart", "loss", "respawn", "counts", "census", "err", "full", "stats_all", "_blockstat",
-                 "_done", "_bs_ring", "x_dep", "x_rlist", "x_rcount", "x_rslot", "x_satt", "x_cno", "x_crq",
-                 "x_srep", "x_nsrep", "x_part", "x_ctl", "x_bstat", "x_hpre", "x_hgrp", "sendbuf", "recvbuf",
-                 "_abuf", "_osrc", "_olist", "_octl", "_ptab", "_osrc1", "_olist1", "_octl1", "_ptab1", "_osync",
-                 "_fw", "_sh_heads", "_sh_nexts", "_sh_cnt", "_sh_send", "_sh_recv", "_census_log"]
-        out = []
-        for k in names:
-            v = getattr(self, k, None)
-            if isinstance(v, list):
-                out.extend(v)
-            elif isinstance(v, torch.Tensor):
-                out.append(v)
-        return out
+    # ------------------------------------------------------------------ HIP graphs (soup_graphs.py)
+    def _state(self, names=None):
+        """The device tensors of ``names`` (DEVICE_STATE: every one a generation reads or writes)."""
+        vals = (getattr(self, k) for k in names or self.DEVICE_STATE)
+        return [t for v in vals if v is not None for t in (v if isinstance(v, list) else [v])]
 
     def _agree(self, ok: bool) -> bool:
         """All ranks agree (MIN) before anything collective depends on a local outcome."""
@@ -1607,82 +1617,19 @@ class SoupEngine:
         return bool(flag.item())
 
     def capture(self, warmup: int = 1, validate: bool = True) -> bool:
-        """Capture the generation for both ping-pong parities in two hipGraphs (ROCm
-        device).  Everything that changes per generation lives in device memory
-        (generation counter, next uid), so replays advance the soup exactly like the
-        eager path.  Sharded engines capture their RCCL collective inside the graph (one
-        all-to-all per generation on the comm stream, joined back); ``validate`` then
-        replays generations from a saved state, compares them bitwise with the eager path
-        on every rank and keeps the graphs only if all ranks agree.  Every rank first agrees
-        that capture succeeded everywhere, so a rank whose capture failed never leaves the
-        others waiting inside a collective."""
-        if self.device.type != "cuda":
-            return False
-        if self.dist.enabled and not self.x2:
-            return False
-        if self.dist.enabled and self.dist.native is None:
-            # torch's process-group collectives are not captured: their watchdog thread
-            # queries events recorded by the capturing stream
-            return False
-        if self.dist.world > 1 and not self.execution.sharded_graph:
-            return False
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        # max(warmup, 1) eager generations in all: the last one runs between the capture of the
-        # multi-generation graphs of the two parities (below)
-        with torch.cuda.stream(s):
-            for _ in range(max(warmup, 1) - 1):
-                self.time += 1
-                self._generation()
-            self._join_side()
-            self._prepare_capture()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        graphs = []
-        p0 = self._p
-        pend0 = self._pending
-        flags0 = self._flags_state()
-        ok = True
-        try:
-            for _ in range(2):
-                g = torch.cuda.CUDAGraph()
-                # thread_local: the process group's watchdog thread keeps querying events
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    self._generation()  # flips self._p during capture (nothing ran)
-                    self._join_side()
-                graphs.append(g)
-        except Exception as e:  # noqa: BLE001 -- any capture failure -> eager generations
-            import sys
-            print(f"soup graph capture failed ({type(e).__name__}: {e}); running eagerly", file=sys.stderr)
-            ok = False
-        self._p = p0
-        self._pending = pend0
-        self._set_flags_state(flags0)  # a capture that failed midway may have advanced them
-        ok = self._agree(ok)
-        if ok and validate:
-            ok = self._agree(self._validate_graphs(graphs if p0 == 0 else graphs[::-1]))
-        if not ok:
-            self._graphs = None
-            self.time += 1  # the last warmup generation, eagerly
-            self._generation()
-            self._join_side()
-            return False
-        # graphs[k] was captured with parity p0 ^ k; index them by parity
-        self._graphs = graphs if p0 == 0 else graphs[::-1]
-        self._chunks = []
-        self._capture_chunk(s, p0, pend0)
-        # the last warmup generation (eager), then the same chunks from the other parity: an
-        # evolve replays multi-generation graphs whatever parity it starts at (an odd
-        # warmup would otherwise leave every later generation on single-generation graphs)
-        with torch.cuda.stream(s):
-            self.time += 1
-            self._generation()
-            self._join_side()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        if self._chunks:
-            self._capture_chunk(s, self._p, self._pending)
-        return True
+        """Capture the generations in hipGraphs (soup_graphs.capture); False: they run eagerly."""
+        return soup_graphs.capture(self, warmup, validate)
+
+    def release_graphs(self):
+        """Drop the captured graphs (soup_graphs.release)."""
+        soup_graphs.release(self)
+
+    def _chunk_sizes(self):
+        return soup_graphs.chunk_sizes(self)
+
+    @property
+    def _chunk(self):  # the largest multi-generation graph, None without one
+        return self._chunks[0] if self._chunks else None
 
     def _prepare_capture(self):
         """The one-time work a first generation does before its graph-captured steady state:
@@ -1697,187 +1644,3 @@ class SoupEngine:
                 a, _, _ = self._gen_args()
                 _lib.run(_lib.OP_SOUP_DECIDE, self.spec, a, self.cfg)
             self._lists_ready = True
-
-    def _chunk_sizes(self):
-        """Generations per multi-generation graph (ExecConfig.graph_chunks, even sizes): an
-        evolve of K generations replays the largest that fit, so a short timed region pays few
-        launches and few finish launches (one 20-generation graph for K = 20, 20 + 20 + 8 + 2
-        for K = 50)."""
-        return sorted({int(x) for x in self.execution.graph_chunks}, reverse=True)
-
-    def _capture_chunk(self, s, p0, pend0):
-        """Multi-generation graphs starting (and ending) at parity p0, added to _chunks
-        (largest first)."""
-        for G in self._chunk_sizes():
-            ch = self._capture_chunk_g(s, p0, pend0, G)
-            if ch is None:
-                break
-            self._chunks.append(ch)
-        self._chunks.sort(key=lambda c: -c[2])
-        self._chunk = self._chunks[0] if self._chunks else None
-
-    def _flags_state(self):
-        return (self._lists_ready, self._pending_fin if not self.x2 else 0, self._census_due)
-
-    def _set_flags_state(self, st):
-        self._lists_ready = st[0]
-        if not self.x2:
-            self._pending_fin = st[1]
-        self._census_due = st[2]
-
-    def _capture_chunk_g(self, s, p0, pend0, G):
-        """A graph of G consecutive generations (G even: it starts and ends at parity
-        p0) replayed as one launch, removing the per-generation graph-launch gap;
-        validated bitwise against G eager generations (all ranks agree or none use it).
-        Reference order with the side-stream plan (ExecConfig.ord_graph_sync): first as TWO
-        graphs -- the G runs + closes, and on the side stream the G plans of the generations
-        after them -- ordered by device counters (SRNN_F_ORD_SYNC) instead of a cross-queue join
-        per generation (~10 us of idle queue each, profiles/r6a); the one-graph form if that
-        capture or its validation fails."""
-        if self._ord_decouple and self._lists_ready and self._streams_concurrent():
-            ch = self._capture_chunk_sync(s, p0, pend0, G)
-            if ch is not None:
-                return ch
-        ok = True
-        gc = torch.cuda.CUDAGraph()
-        flags0 = self._flags_state()
-        try:
-            with torch.cuda.graph(gc, stream=s, capture_error_mode="thread_local"):
-                for _ in range(G):
-                    self._generation()
-                self._join_side()
-        except Exception as e:  # noqa: BLE001
-            import sys
-            print(f"multi-generation graph capture failed ({type(e).__name__}: {e})", file=sys.stderr)
-            ok = False
-        self._p, self._pending = p0, pend0
-        self._set_flags_state(flags0)
-        ok = self._agree(ok)
-        if ok:
-            ok = self._agree(self._validate_replay(lambda: gc.replay(), G, parity_after=p0))
-        return (gc, p0, G, None) if ok else None
-
-    def _streams_concurrent(self) -> bool:
-        """(once per engine) whether kernels on the side stream and the current one run at the same
-        time -- a two-graph chunk's counters need it: under a profiler that serialises kernels
-        (rocprofv3 --pmc) or on a shared hardware queue every wait would run into its timeout.
-        Agreed over the ranks."""
-        if getattr(self, "_conc", None) is None:
-            ok = _lib.streams_concurrent(self._ord_side, torch.cuda.current_stream(self.device), self.device)
-            if not ok:
-                import sys
-                print("side stream does not run beside the current one (serialising profiler?): "
-                      "one-graph chunks", file=sys.stderr)
-            self._conc = self._agree(ok)
-        return self._conc
-
-    def _capture_chunk_sync(self, s, p0, pend0, G):
-        """The two-graph form of a G-generation chunk (see _capture_chunk_g): main graph = G x
-        (run + close, the close waiting for the next plan) + the batched finish; side graph = G x
-        (gate on the run counter, plan of the next generation, done count)."""
-        gc, gs = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        flags0 = self._flags_state()
-        ok = True
-        self._sync = True
-        try:
-            with torch.cuda.graph(gc, stream=s, capture_error_mode="thread_local"):
-                for _ in range(G):
-                    self._generation()
-                self._join_side()
-            self._p = p0
-            with torch.cuda.graph(gs, stream=self._ord_side, capture_error_mode="thread_local"):
-                for g in range(G):
-                    self._p = p0 ^ (g & 1)
-                    _lib.run(_lib.OP_ORD_PLAN, self.spec, self._plan_args(True), self.cfg)
-        except Exception as e:  # noqa: BLE001
-            import sys
-            print(f"two-graph capture failed ({type(e).__name__}: {e}); one graph", file=sys.stderr)
-            ok = False
-        finally:
-            self._sync = False
-        self._p, self._pending = p0, pend0
-        self._set_flags_state(flags0)
-        ch = (gc, p0, G, gs)
-        ok = self._agree(ok)
-        if ok:
-            ok = self._agree(self._validate_replay(lambda: self._replay_chunk(ch), G, parity_after=p0,
-                                                   ring=self.finish_mode == "batch"))
-        return ch if ok else None
-
-    def _replay_chunk(self, ch):
-        """Replay a multi-generation chunk; a two-graph chunk's side graph first, on the side stream
-        (after the work already queued on this one: its first plan overwrites the set of the
-        generation before the chunk), the two then run on their own, ordered by the counters."""
-        if ch[3] is not None:
-            main = torch.cuda.current_stream(self.device)
-            self._ord_side.wait_stream(main)
-            with torch.cuda.stream(self._ord_side):
-                ch[3].replay()
-        ch[0].replay()
-
-    def release_graphs(self):
-        """Drop the captured graphs (before tearing down the process group: an RCCL
-        communicator must not be destroyed while graph executables still reference it)."""
-        if self._graphs is not None or self._chunks:
-            torch.cuda.synchronize(self.device)
-            for g in (self._graphs or []) + [c[0] for c in self._chunks] + [c[3] for c in self._chunks if c[3]]:
-                g.reset()
-            self._graphs = None
-            self._chunk = None
-            self._chunks = []
-
-    def _validate_graphs(self, graphs) -> bool:
-        def replay():
-            for _ in range(2):
-                graphs[self._p].replay()
-                self._p = 1 - self._p
-        return self._validate_replay(replay, 2)
-
-    def _validate_replay(self, replay, gens: int, parity_after=None, ring: bool = False) -> bool:
-        """Run ``gens`` eager generations from the current state, restore it, run
-        ``replay`` (the captured equivalent), compare bitwise, restore again."""
-        state = self._state()
-        saved = [t.clone() for t in state]
-        p0, pend0, t0 = self._p, self._pending, self.time
-        flags0 = self._flags_state()
-        for _ in range(gens):
-            self._generation()
-        self._join_side()
-        torch.cuda.synchronize(self.device)
-        flags1 = self._flags_state()
-        eager = [t.clone() for t in state]
-        for t, v in zip(state, saved):
-            t.copy_(v)
-        self._p, self._pending = p0, pend0
-        self._set_flags_state(flags0)
-        replay()
-        if parity_after is not None:
-            self._p = parity_after
-        self._set_flags_state(flags1)
-        torch.cuda.synchronize(self.device)
-        # compare the semantic state only: exchange-buffer row order and the attack
-        # lists' link order follow atomics and legitimately differ between runs
-        keep = {id(t) for t in self._bufs} | {id(getattr(self, k)) for k in (
-            "uid", "next_uid", "_gen_ring", "counts", "census", "loss", "respawn", "action", "counterpart", "err")
-            if isinstance(getattr(self, k, None), torch.Tensor)}
-        if parity_after is not None and self._census_log is not None:
-            # (a chunk finishes its generations in the launches the eager generations use, so the census
-            # log rows agree; two single-generation graphs finish one by one, the eager pair at once)
-            keep.add(id(self._census_log))
-        if ring and isinstance(getattr(self, "_bs_ring", None), torch.Tensor):
-            # (a chunk batches its finishes like the eager generations: every generation's census and
-            # ballots, wherever they ran, compared too)
-            keep.add(id(self._bs_ring))
-        same = all(torch.equal(x.view(torch.uint8), y.view(torch.uint8))
-                   for x, y in zip(state, eager) if id(x) in keep)
-        # (reference order: and no error bit the eager generations did not raise either)
-        for ctl in (self._octl, self._octl1) if self.order == "sequential" else ():
-            if ctl is not None:
-                i = next(k for k, x in enumerate(state) if x is ctl)
-                same = same and int(ctl[_lib.ORD_ERRW]) == int(eager[i][_lib.ORD_ERRW])
-        for t, v in zip(state, saved):
-            t.copy_(v)
-        self._p, self._pending, self.time = p0, pend0, t0
-        self._set_flags_state(flags0)
-        torch.cuda.synchronize(self.device)
-        return same

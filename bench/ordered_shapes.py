@@ -11,6 +11,16 @@ in the shape list but not in the default ``--shapes``: its lane steps outlast th
 synchronous (Jacobi) soup of the same shape with the wave kernels on and off, and the host serial
 loop (``SequentialSoupEngine``) at 2,000 particles scaled per particle.
 
+``ordered-sharded`` times the generation sharded over ranks (csrc/srnn_generic.hip g_soup_ordered_sh)
+on the one-rank timing model of 8 ranks (``ExecConfig(ordsh_emulate=8)`` on a one-rank gloo group):
+the rank plans every turn, runs 1/8 of the turns of every level and packs, gathers and unpacks their
+records.  The model's all-gather never leaves the box -- gloo stages the device records through host
+memory -- so inter-GPU transfer time is not in it; the step reports the record bytes of each level
+instead.  The rows of the model are invalid by design (a sticky error bit): the step reads the error
+word and never calls ``count()``.  The driver runs the step twice, with the wave forms of the level
+launches and (``ordered-sharded-lane``) with ``--ord-wave 0``; ``ordered-eager`` of the same run is
+the single-rank generation to compare with (profiles/ordered_sharded_runtime_shapes.md).
+
 The driver runs every step in a child process of its own under a time limit and stops at the
 first step that fails; each step prints one JSON line.  ``--markdown`` adds the table of
 profiles/ordered_runtime_shapes.md.
@@ -36,6 +46,8 @@ SHAPES = {"ww33": ("weightwise", (3, 3)), "ww103": ("weightwise", (10, 3)), "ww1
           "rnn82": ("recurrent", (8, 2)), "rnn162": ("recurrent", (16, 2))}
 DEFAULT_SHAPES = tuple(k for k in SHAPES if k != "rnn162")
 STEPS = ("ordered-eager", "ordered-graph", "sync-waves", "sync-lanes", "host-serial")
+SHARDED_STEPS = ("ordered-sharded", "ordered-sharded-lane")  # (not in the default --steps)
+EMULATED_RANKS = 8
 
 
 def _spec(shape):
@@ -72,6 +84,8 @@ def step(name, shape, n, gens, host_n, ord_wave=None):
         return out
     if not torch.cuda.is_available():
         raise SystemExit("ordered_shapes: no GPU (a measurement does not fall back to the host)")
+    if name in SHARDED_STEPS:
+        return sharded_step(out, spec, n, gens, False if name.endswith("-lane") else ord_wave)
     if name.startswith("ordered"):
         ex = ExecConfig(graph_chunks=(2,), ord_wave=ord_wave)
         ex.apply_library()
@@ -98,10 +112,54 @@ def step(name, shape, n, gens, host_n, ord_wave=None):
     return out
 
 
+def sharded_step(out, spec, n, gens, ord_wave):
+    """The 8-rank timing model of the sharded generation: construct, one untimed generation, `gens`
+    timed ones, the error word (never count(): the model's rows are invalid by design)."""
+    import socket
+
+    import torch
+    import torch.distributed as dist
+    from self_replicating_neural_networks_amd.config import ExecConfig
+    from self_replicating_neural_networks_amd.ops import _lib
+    from self_replicating_neural_networks_amd.parallel.dist import Dist
+    from self_replicating_neural_networks_amd.soup_engine import ORD_ERR_EMULATED, SoupEngine
+
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    try:
+        ex = ExecConfig(ordsh_emulate=EMULATED_RANKS, ord_wave=ord_wave)
+        ex.apply_library()
+        e = SoupEngine(spec, n, PARAMS, device="cuda", seed=1, order="sequential", execution=ex,
+                       dist=Dist(0, 1, 0, None, force=True))
+        assert _lib.is_generic(spec, _lib.OP_SOUP_ORDERED_SH, e.dtype_code), "not a runtime shape"
+        e.evolve(1)
+        ms = _timed(e, gens)
+        err = e.ordered_error()
+        assert err == ORD_ERR_EMULATED, f"error word {err}: only the model's own bit may be set"
+        lv = e._osrc[:4 * n].view(n, 4)[:, 3]
+        own = -(-n // EMULATED_RANKS)
+        maxl = int(e._octl[_lib.ORD_MAXLW].item())
+        per_level = torch.bincount(lv.clamp(min=0).long(), minlength=maxl + 1)[:maxl + 1].tolist()
+        own_level = torch.bincount(lv[:own].clamp(min=0).long(), minlength=maxl + 1)[:maxl + 1].tolist()
+        out.update(n=n, ms_per_gen=round(ms, 3), ranks=EMULATED_RANKS, form=e.ordered_sharded_form(),
+                   max_level=maxl, turns_per_level=per_level, own_turns_per_level=own_level, record_bytes=e._sh_recb,
+                   gathered_mb_per_level=[round(c * e._sh_recb / 2 ** 20, 2) for c in per_level],
+                   scratch_mb=round(e._scratch.numel() / 2 ** 20, 1))
+    finally:
+        dist.destroy_process_group()
+    return out
+
+
 def markdown(rows, n):
     by = {}
     for r in rows:
         by.setdefault(r["shape"], {})[r["step"]] = r
+    if any(r["step"] in SHARDED_STEPS for r in rows):
+        return sharded_markdown(by)
     lines = [f"| shape | P | ordered eager ms | ordered graph ms | levels (+tail) | sync waves ms | sync lanes ms | "
              f"host loop ms (scaled to {n}) | device vs host |", "|---|---|---|---|---|---|---|---|---|"]
     for shape, d in by.items():
@@ -116,13 +174,32 @@ def markdown(rows, n):
     return "\n".join(lines)
 
 
+def sharded_markdown(by):
+    lines = ["| shape | P | single rank ms | 8-rank model ms (wave forms) | 8-rank model ms (lane form) | single / model | "
+             "levels | turns per level | gathered MiB per level |", "|---|---|---|---|---|---|---|---|---|"]
+    for shape, d in by.items():
+        g = lambda k, f="ms_per_gen": d.get(k, {}).get(f, "not measured")  # noqa: E731
+        w, l = d.get("ordered-sharded", {}), d.get("ordered-sharded-lane", {})
+        o = w or l
+        ms = [x["ms_per_gen"] for x in (w, l) if x]
+        one = d.get("ordered-eager", {}).get("ms_per_gen")
+        ratio = f"{one / min(ms):.2f}x" if one and ms else "not measured"
+        wave = f"{w['ms_per_gen']} ({w['form']})" if w else "not measured"
+        lines.append(f"| {shape} | {o.get('P', '')} | {g('ordered-eager')} | {wave} | {g('ordered-sharded-lane')} | {ratio} | "
+                     f"{o.get('max_level', 0) + 1 if o else ''} | {o.get('turns_per_level', '')} | "
+                     f"{o.get('gathered_mb_per_level', '')} |")
+    return "\n".join(lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=100000)
     ap.add_argument("--gens", type=int, default=3)
     ap.add_argument("--host-n", type=int, default=2000)
     ap.add_argument("--shapes", default=",".join(DEFAULT_SHAPES))
-    ap.add_argument("--steps", default=",".join(STEPS))
+    ap.add_argument("--steps", default=",".join(STEPS),
+                    help="also: ordered-sharded (the driver runs it with the wave forms and, as ordered-sharded-lane, "
+                         "with --ord-wave 0)")
     ap.add_argument("--step-timeout", type=int, default=150)
     ap.add_argument("--ord-wave", type=int, choices=(0, 1), default=None,
                     help="reference-order turns of the wide Weightwise shapes on lane groups and of the wide "
@@ -137,7 +214,10 @@ def main():
         return 0
     rows = []
     for shape in args.shapes.split(","):
-        for name in args.steps.split(","):
+        names = []
+        for name in args.steps.split(","):  # (the sharded step: once per form of the level launches)
+            names += list(SHARDED_STEPS) if name == "ordered-sharded" else [name]
+        for name in names:
             cmd = [sys.executable, os.path.abspath(__file__), "--n", str(args.n), "--gens", str(args.gens), "--host-n",
                    str(args.host_n), "--child", name, shape]
             if args.ord_wave is not None:

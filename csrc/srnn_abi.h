@@ -320,6 +320,14 @@ int srnn_generic_supports(const SrnnCfg* cfg, int op, int dev);
 // Weightwise) or a wave (wide Recurrent) per turn
 int srnn_ord_run_form(const SrnnCfg* cfg, int dev);
 int srnn_generic_ord_run_form(const SrnnCfg* cfg, int dev);
+// the sharded reference-order generation (OP_SOUP_ORDERED_SH) of this configuration: the form of its
+// level launches on the host (dev 0) / device (dev 1), the knobs in force counted (0 none, 1 a lane per
+// turn, 2 a group of lanes / a wave per turn: the runtime shapes of the wave runs), and the device
+// scratch bytes a rank with `own` turns needs for a runtime shape (the level list, the lanes of the
+// level and close launches, the recurrent wave slices; -1: not a valid shape)
+int srnn_ordsh_form(const SrnnCfg* cfg, int dev);
+int srnn_generic_ordsh_form(const SrnnCfg* cfg, int dev);
+int64_t srnn_generic_ordsh_scratch_bytes(const SrnnCfg* cfg, int64_t own);
 // the kernel family that serves OP_TRAIN of this configuration on the host (dev 0) / device (dev 1),
 // the knobs in force counted: 0 none, 1 a lane per particle, 2 a wave / row kernel (the wide
 // Weightwise and Recurrent runtime shapes, the big aggregating nets)

@@ -153,6 +153,9 @@ static int route(int op, const SrnnCfg* c, const SrnnArgs* a) {
       const bool host = a && !a->dev;
       if (host) return 1;  // wave-per-particle paths are GPU only
       if (k == 1 && srnn_aggbig_serves(op, c->dtype, c->shuffler)) return 0;
+      // (the classify that closes a generation of the all-gather exchange -- respawn count, generation
+      // counter -- is the runtime-shape engine's: k_wide's classify only counts the classes)
+      if (k == 2 && op == OP_CLASSIFY && a && (a->flags & (SRNN_F_COUNT_RESPAWNS | SRNN_F_GEN_ADVANCE))) return 1;
       if (k == 2 && (op == OP_INIT || op == OP_APPLY || op == OP_RUN_FIXPOINT || op == OP_CLASSIFY)) return 0;
       return 1;
     }
@@ -190,8 +193,10 @@ static int with_scratch(int op, const SrnnCfg* c, const SrnnArgs* a) {
     return dispatch(op, c, a);
   // (a reference-order generation: one lane per turn of its run launch; a plan needs none)
   if (op == OP_ORD_PLAN || op == OP_GEN_FINISH) return dispatch(op, c, a);
-  const int64_t want = op == OP_SOUP_ORDERED ? srnn_generic_ord_scratch_bytes(c, a->n)
-                                             : srnn_generic_scratch_bytes(c, a->n, 65536);
+  // (a sharded one: the lanes of this rank's own turns)
+  const int64_t want = op == OP_SOUP_ORDERED      ? srnn_generic_ord_scratch_bytes(c, a->n)
+                       : op == OP_SOUP_ORDERED_SH ? srnn_generic_ordsh_scratch_bytes(c, a->o_hi - a->o_lo)
+                                                  : srnn_generic_scratch_bytes(c, a->n, 65536);
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64) dev = 0;
@@ -300,6 +305,17 @@ int srnn_ord_run_form(const SrnnCfg* cfg, int dev) {
   const int r = route(OP_SOUP_ORDERED, cfg, &probe);
   if (r == 0) return 1;
   return r == 1 ? srnn_generic_ord_run_form(cfg, dev) : 0;
+}
+
+// the form of the level launches of a sharded reference-order generation (OP_SOUP_ORDERED_SH): 0 none,
+// 1 a lane per turn (the lane templates' k_ordsh_level, the runtime shapes' k_gordsh_level), 2 a group
+// of lanes / a wave per turn (srnn_generic.hip k_gordsh_level_ww / k_gordsh_level_rnn)
+int srnn_ordsh_form(const SrnnCfg* cfg, int dev) {
+  SrnnArgs probe{};
+  probe.dev = dev;
+  const int r = route(OP_SOUP_ORDERED_SH, cfg, &probe);
+  if (r == 0) return 1;
+  return r == 1 ? srnn_generic_ordsh_form(cfg, dev) : 0;
 }
 
 // the kernel family that serves OP_TRAIN of this configuration on the host (dev 0) / device (dev 1),

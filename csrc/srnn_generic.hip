@@ -2892,6 +2892,19 @@ static bool gord_serves(const GShape& s, int op, bool dev, const char** why) {
   return true;
 }
 
+// host: f(x, i) on a worker of the thread pool, each worker its own stride-1 scratch
+template <class F>
+static auto g_host_ctx(const GShape& s, const float* coords, F f) {
+  return [&s, coords, f](int64_t i) {
+    thread_local std::vector<float> buf;
+    thread_local std::vector<double> orth;
+    if (buf.size() < (size_t)s.sfloats) buf.resize((size_t)s.sfloats);
+    if (orth.size() < (size_t)s.orthd + 1) orth.resize((size_t)s.orthd + 1);
+    GCtx x{&s, buf.data(), 1, coords, orth.data()};
+    return f(x, i);
+  };
+}
+
 // OP_SOUP_ORDERED of a runtime shape: the shared checks, host generation and launch sequence
 // (srnn_ordered.h) with this engine's turn, close and scratch
 static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) {
@@ -2905,16 +2918,7 @@ static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) 
     const int32_t gen = GOrd::Dec::gen_of(a);
     std::vector<float> coords((size_t)(3 * s.P + 3));
     if (s.kind == 0) make_coords_host(s, coords.data());
-    auto with_ctx = [&](auto&& f) {  // each worker its own stride-1 scratch
-      return [&, f](int64_t i) {
-        thread_local std::vector<float> buf;
-        thread_local std::vector<double> orth;
-        if (buf.size() < (size_t)s.sfloats) buf.resize((size_t)s.sfloats);
-        if (orth.size() < (size_t)s.orthd + 1) orth.resize((size_t)s.orthd + 1);
-        GCtx x{&s, buf.data(), 1, coords.data(), orth.data()};
-        return f(x, i);
-      };
-    };
+    auto with_ctx = [&](auto&& f) { return g_host_ctx(s, coords.data(), f); };
     ord_generation_host<GORD_RB>(
         a, with_ctx([&](const GCtx& x, int64_t k) { GOrd::turn(x, a, k, gen); }),
         with_ctx([&](const GCtx& x, int64_t r) -> int8_t {
@@ -2943,6 +2947,361 @@ static int g_soup_ordered(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) 
   return ord_generation_dev<GOrdPol>(c, s, a, 12, [&](hipStream_t st) {
     hipLaunchKernelGGL(k_gord_head, dim3(1), dim3(64), 0, st, s, a);
   });
+}
+
+// ==================================================================================
+// The reference-order generation of a runtime shape sharded over ranks (OP_SOUP_ORDERED_SH): the
+// level-synchronous protocol of srnn_ordered_sh.h -- the same six phases in the same global view
+// (n = n_total, lo = 0, own turns [o_lo, o_hi), W2 the gathered generation-start table, W / W3 the
+// version tables of all rows) -- with this engine's turn and close (GOrd).  Plan, levels and link
+// are the shape-independent kernels of srnn_ordered.h / srnn_ordered_sh.h at recompute depth 0.
+//
+// A level is ONE launch over this rank's turns of that level; nothing in it waits for another
+// workgroup (no ord::publish, no records handed over, no counters): the next level starts after
+// the unpack on the same stream.  Three forms, chosen as g_soup_ordered chooses its run:
+//   lane   k_gordsh_level      a lane per own turn (dense over [o_lo, o_hi)), GOrd::turn
+//   group  k_gordsh_level_ww   gord_ww_turn on U lanes per turn, G turns per wave (gord_wave_serves)
+//   wave   k_gordsh_level_rnn  gord_rnn_turn on a wave per turn (gord_rnn_serves, slices that fit)
+// The group and wave forms take their turns from the compact list of this rank's turns of the
+// level (k_gordsh_list: ord::wave_append -- the order within a level changes no value), so a wave
+// is full of work at the sparse deep levels too; SrnnArgs.x_blk bounds the list's length (the
+// per-level counts the caller reads back anyway) and sizes the launch.
+//
+// Scratch of a rank with `own` turns: [GORD_HDR bytes: word 0 the length of the level list]
+// [the list: own int32, padded to 256 bytes] [the lanes of the level / close launch (element-major
+// vectors, then the orthogonal-init doubles), or the BPTT / orthogonal-init slices of the wave
+// form, one per workgroup of the launch: at most GSH_MAX_WAVES, the list is walked grid-stride].
+// ==================================================================================
+constexpr int64_t GSH_MAX_WAVES = 8192;  // workgroups (= scratch slices) of a recurrent level launch
+
+static int64_t gsh_lanes(int64_t own) { return std::max<int64_t>((own + TB - 1) / TB * TB, GTB); }
+SRNN_HD int64_t gsh_list_bytes(int64_t own) { return ((own > 1 ? own : 1) * 4 + 255) & ~(int64_t)255; }
+static int64_t gsh_rnn_waves(int64_t own) { return std::max<int64_t>(std::min<int64_t>(own, GSH_MAX_WAVES), 1); }
+static int64_t gsh_scratch_bytes(const GShape& s, int64_t own) {
+  int64_t body = gsh_lanes(own) * g_lane_bytes(s);
+  if (rw_shape_serves(s)) body = std::max<int64_t>(body, gsh_rnn_waves(own) * rw_soup_scratch_bytes(s));
+  return GORD_HDR + gsh_list_bytes(own) + body;
+}
+SRNN_HD int32_t* gsh_list(const SrnnArgs& a) {
+  return reinterpret_cast<int32_t*>(reinterpret_cast<char*>(a.scratch) + GORD_HDR);
+}
+SRNN_HD char* gsh_base(const SrnnArgs& a) {
+  return reinterpret_cast<char*>(a.scratch) + GORD_HDR + gsh_list_bytes(a.o_hi - a.o_lo);
+}
+
+// which runtime shapes have a sharded reference-order generation: those of gord_serves but the
+// big aggregating nets (their single-rank generation is BigOrd's, srnn_bignet.h, not GOrd's)
+static bool gordsh_serves(const GShape& s, bool dev, const char** why) {
+  if (s.kind == 1 && s.P > 64) {
+    *why = "the big aggregating nets (aggregating, P > 64) have no sharded reference-order generation";
+    return false;
+  }
+  return gord_serves(s, OP_SOUP_ORDERED, dev, why);
+}
+
+// lane form: own turn o_lo + i on lane i of the launch, if its level is L
+__global__ __launch_bounds__(TB) void k_gordsh_level(GShape s, SrnnArgs a, int32_t L) {
+  __shared__ float s_coords[3 * GORD_MAXP];
+  if (s.kind == 0) make_coords_dev(s, s_coords);
+  const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x, k = a.o_lo + i;
+  if (k >= a.o_hi || a.o_src[4 * k + 3] != L) return;
+  const int64_t lanes = (int64_t)gridDim.x * TB;
+  char* base = gsh_base(a);
+  GCtx x{&s, reinterpret_cast<float*>(base) + i, lanes, s_coords, g_orth(s, base, lanes, i)};
+  GOrd::turn(x, a, k, GOrd::Dec::gen_of(a));
+}
+
+// the compact list of this rank's turns of level L (its length: word 0 of the scratch, zeroed on
+// the stream before this launch)
+__global__ __launch_bounds__(TB) void k_gordsh_list(SrnnArgs a, int32_t L) {
+  const int64_t k = a.o_lo + (int64_t)blockIdx.x * TB + threadIdx.x;
+  const bool mine = k < a.o_hi && a.o_src[4 * k + 3] == L;
+  const int32_t pos = ord::wave_append(reinterpret_cast<int32_t*>(a.scratch), mine);
+  if (mine) gsh_list(a)[pos] = (int32_t)k;  // (pos < o_hi - o_lo: every own turn is appended at most once)
+}
+
+// group form: one wave holds G turns of the list at a time (grid-stride over the list); a group past
+// the end of the list passes k = -1, so that every lane reaches every barrier of the turn
+template <int WT = 0, int DT = 0>
+__global__ __launch_bounds__(64) void k_gordsh_level_ww(GShape s, WWave g, SrnnArgs a) {
+  extern __shared__ float sm[];
+  float* coords = sm;  // [P][3], whole workgroup
+  make_coords_dev(s, coords);
+  const int lane = threadIdx.x, u = lane % g.U, grp = lane / g.U;
+  WWGroup R = ww_group(s, g, sm, grp);
+  const bool shuffle = (a.flags & SRNN_F_SHUFFLE) != 0;
+  const Rng rng = GItem::rng(a);
+  const unsigned long long gm = (g.U == 64 ? ~0ull : ((1ull << g.U) - 1ull)) << (grp * g.U);
+  const int32_t gen = GOrd::Dec::gen_of(a);
+  const int64_t cnt = *reinterpret_cast<const int32_t*>(a.scratch);
+  const int32_t* list = gsh_list(a);
+  for (int64_t i0 = (int64_t)blockIdx.x * g.G; i0 < cnt; i0 += (int64_t)gridDim.x * g.G) {  // (wave uniform)
+    const int64_t i = i0 + grp;
+    gord_ww_turn<WT, DT>(s, g, a, R, coords, u, gm, i < cnt ? (int64_t)list[i] : -1, gen, shuffle, rng);
+    __syncthreads();  // (the group's LDS regions are reloaded by the next turn)
+  }
+}
+
+// wave form: one turn of the list per wave at a time (grid-stride over the list); workgroup b owns the
+// BPTT / orthogonal-init slice b of the scratch -- its position in the launch, not the turn's slot
+template <int WT, int DT>
+__global__ __launch_bounds__(64) void k_gordsh_level_rnn(GShape s, SrnnArgs a) {
+  extern __shared__ float sm[];
+  const RWave r = rw_layout(s, sm);
+  char* scr = gsh_base(a) + (int64_t)blockIdx.x * rw_soup_scratch_bytes(s);
+  float* hs = reinterpret_cast<float*>(scr);
+  double* orth = reinterpret_cast<double*>(scr + (((int64_t)s.P * s.HS + 1) & ~(int64_t)1) * 4);
+  const int32_t gen = GOrd::Dec::gen_of(a);
+  const int64_t cnt = *reinterpret_cast<const int32_t*>(a.scratch);
+  const int32_t* list = gsh_list(a);
+  for (int64_t i = blockIdx.x; i < cnt; i += gridDim.x) {
+    gord_rnn_turn<WT, DT>(s, a, r, hs, orth, (int64_t)list[i], gen);
+    __syncthreads();  // (the LDS rows are reloaded by the next turn)
+  }
+}
+
+// exchange records {int64 slot, pad to 16 bytes | E row | A row} of this rank's level-L outputs: a
+// wave looks at 64 own turns, then copies the rows of each one it packs with all its lanes (rows
+// are PP elements of the table's format: whole 8-byte words)
+__global__ __launch_bounds__(TB) void k_gordsh_pack(GShape s, SrnnArgs a, int32_t L) {
+  const int64_t rw = g_rb(s) / 8, recb = ordsh::HDR + 2 * g_rb(s);
+  const int lane = threadIdx.x;
+  const int64_t k = a.o_lo + (int64_t)blockIdx.x * TB + lane;
+  bool mine = k < a.o_hi && a.o_src[4 * k + 3] == L;
+  const int32_t pos = ord::wave_append(a.x_ctl, mine);
+  if (mine && (int64_t)pos >= a.x_blk) {  // the caller sized the buffer for this level: a bug
+    atomicOr(a.o_ctl + ord::ERRW, ord::ERR_PACK);
+    mine = false;
+  }
+  for (unsigned long long m = __ballot(mine); m; m &= m - 1) {
+    const int src = (int)__ffsll((long long)m) - 1;
+    const int64_t kk = __shfl(k, src);
+    uint64_t* r = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(a.sendbuf) + (int64_t)__shfl(pos, src) * recb);
+    if (lane == 0) r[0] = (uint64_t)kk;
+    const uint64_t* e = reinterpret_cast<const uint64_t*>(GItem::rowp(s, a.W, kk));
+    for (int64_t q = lane; q < rw; q += TB) r[2 + q] = e[q];
+    if (ord::stored(a, kk)) {
+      const uint64_t* o = reinterpret_cast<const uint64_t*>(GItem::rowp(s, a.W3, kk));
+      for (int64_t q = lane; q < rw; q += TB) r[2 + rw + q] = o[q];
+    }
+  }
+}
+
+// the gathered records (every rank's; this rank's own rows are already in place) into W / W3
+__global__ __launch_bounds__(TB) void k_gordsh_unpack(GShape s, SrnnArgs a, int64_t nrec) {
+  const int64_t rw = g_rb(s) / 8, recb = ordsh::HDR + 2 * g_rb(s);
+  const int lane = threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * TB + lane;
+  if (blockIdx.x == 0 && lane == 0) a.x_ctl[0] = 0;  // the next level's pack counter
+  int64_t k = -1;
+  if (i < nrec) k = *reinterpret_cast<const int64_t*>(reinterpret_cast<const char*>(a.recvbuf) + i * recb);
+  const bool take = k >= 0 && k < a.n && !(k >= a.o_lo && k < a.o_hi);
+  for (unsigned long long m = __ballot(take); m; m &= m - 1) {
+    const int src = (int)__ffsll((long long)m) - 1;
+    const int64_t kk = __shfl(k, src);
+    const uint64_t* r = reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(a.recvbuf) +
+                                                          ((int64_t)blockIdx.x * TB + src) * recb);
+    uint64_t* e = reinterpret_cast<uint64_t*>(GItem::rowp(s, a.W, kk));
+    for (int64_t q = lane; q < rw; q += TB) e[q] = r[2 + q];
+    if (ord::stored(a, kk)) {
+      uint64_t* o = reinterpret_cast<uint64_t*>(GItem::rowp(s, a.W3, kk));
+      for (int64_t q = lane; q < rw; q += TB) o[q] = r[2 + rw + q];
+    }
+  }
+}
+
+// this rank's rows: final version into W, respawn flag for the uid assignment (a lane per own row)
+__global__ __launch_bounds__(TB) void k_gordsh_close(GShape s, SrnnArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x, r = a.o_lo + i;
+  if (r >= a.o_hi) return;
+  if (a.o_src[4 * r + 3] < 0) atomicOr(a.o_ctl + ord::ERRW, ord::ERR_NOT_RUN);
+  const int64_t lanes = (int64_t)gridDim.x * TB;
+  char* base = gsh_base(a);
+  GCtx x{&s, reinterpret_cast<float*>(base) + i, lanes, nullptr, g_orth(s, base, lanes, i)};
+  GOrd::close_row(x, a, r, x.v(s.o_w));
+  if (a.rowflags) a.rowflags[r] = a.respawn[r] != 0;
+}
+
+template <int WT, int DT>
+static void gordsh_ww_launch_shape(dim3 grid, size_t lds, hipStream_t st, const GShape& s, const WWave& g,
+                                   const SrnnArgs& a) {
+  hipLaunchKernelGGL((k_gordsh_level_ww<WT, DT>), grid, dim3(64), lds, st, s, g, a);
+}
+// `turns` bounds the list's length; the register-SGD instantiations of gord_ww_launch
+static void gordsh_ww_launch(const GShape& s, const WWave& g, const SrnnArgs& a, int64_t turns, hipStream_t st) {
+  const dim3 grid((unsigned)std::max<int64_t>((turns + g.G - 1) / g.G, 1));
+  const size_t lds = ww_ord_lds(s, g);
+  const bool reg = knob(SRNN_KNOB_WW_WAVE, 1) != 2;
+  const int w = reg ? s.W : 0, d = reg ? s.D : 0;
+  if (w == 3 && d == 3 && g.U == 4) gordsh_ww_launch_shape<3, 3>(grid, lds, st, s, g, a);
+  else if (w == 3 && d == 4 && g.U == 4) gordsh_ww_launch_shape<3, 4>(grid, lds, st, s, g, a);
+  else if (w == 10 && d == 2 && g.U == 16) gordsh_ww_launch_shape<10, 2>(grid, lds, st, s, g, a);
+  else if (w == 10 && d == 3 && g.U == 16) gordsh_ww_launch_shape<10, 3>(grid, lds, st, s, g, a);
+  else if (w == 16 && d == 2 && g.U == 16) gordsh_ww_launch_shape<16, 2>(grid, lds, st, s, g, a);
+  else if (w == 16 && d == 3 && g.U == 16) gordsh_ww_launch_shape<16, 3>(grid, lds, st, s, g, a);
+  else gordsh_ww_launch_shape<0, 0>(grid, lds, st, s, g, a);
+}
+// one wave per turn of the list, at most GSH_MAX_WAVES of them; rw_launch's instantiations
+static void gordsh_rnn_launch(const GShape& s, const SrnnArgs& a, int64_t waves, hipStream_t st) {
+  const dim3 grid((unsigned)waves), block(64);
+  const size_t lds = gord_rnn_lds(s);
+  const bool spec = knob(SRNN_KNOB_RNN_SPEC, 1) != 0;
+  const int w = spec ? s.W : 0, d = spec ? s.D : 0;
+  if (w == 8 && d == 2) hipLaunchKernelGGL((k_gordsh_level_rnn<8, 2>), grid, block, lds, st, s, a);
+  else if (w == 16 && d == 2) hipLaunchKernelGGL((k_gordsh_level_rnn<16, 2>), grid, block, lds, st, s, a);
+  else if (w == 32 && d == 2) hipLaunchKernelGGL((k_gordsh_level_rnn<32, 2>), grid, block, lds, st, s, a);
+  else if (w == 8 && d == 3) hipLaunchKernelGGL((k_gordsh_level_rnn<8, 3>), grid, block, lds, st, s, a);
+  else if (w == 16 && d == 3) hipLaunchKernelGGL((k_gordsh_level_rnn<16, 3>), grid, block, lds, st, s, a);
+  else hipLaunchKernelGGL((k_gordsh_level_rnn<0, 0>), grid, block, lds, st, s, a);
+}
+
+// OP_SOUP_ORDERED_SH of a runtime shape: one phase (SrnnArgs.steps) of the generation
+static int g_soup_ordered_sh(const SrnnCfg& c, const GShape& s, const SrnnArgs& a) {
+  using Dec = GOrd::Dec;
+  using ShapeFree = Weightwise<1, 1>;  // (the level propagation and the link read no shape)
+  const int phase = a.steps;
+  if (a.lo != 0 || a.n_total != a.n || a.n >= (int64_t)(1 << 30) || a.o_lo < 0 || a.o_hi < a.o_lo || a.o_hi > a.n) {
+    set_error("sharded ordered generation: the global view (lo 0, n = n_total < 2^30) and 0 <= o_lo <= o_hi <= n");
+    return -5;
+  }
+  if (!a.W || !a.W2 || !a.W3 || !a.o_src || !a.o_list || !a.o_ctl || !a.heads || !a.nexts || !a.respawn ||
+      phase < ordsh::PLAN || phase > ordsh::LINK) {
+    set_error("sharded ordered generation needs W, W2, W3, o_src, o_list, o_ctl, the attack lists, respawn and a "
+              "phase 0..5");
+    return -5;
+  }
+  if ((phase == ordsh::PACK && (!a.sendbuf || !a.x_ctl)) || (phase == ordsh::UNPACK && (!a.recvbuf || !a.x_ctl)) ||
+      (phase == ordsh::LINK && (!a.heads_next || !a.nexts_next))) {
+    set_error("sharded ordered generation: pack needs sendbuf + x_ctl, unpack recvbuf + x_ctl, link the next lists");
+    return -5;
+  }
+  const int32_t gen = Dec::gen_of(a);
+  const int32_t L = a.o_levels;
+  const int64_t own = a.o_hi - a.o_lo;
+  const int64_t rb = g_rb(s), recb = ordsh::HDR + 2 * rb;
+  const int64_t nrec = phase == ordsh::UNPACK ? (int64_t)a.world * a.x_blk : 0;
+  if (!a.dev) {
+    std::vector<float> coords((size_t)(3 * s.P + 3));
+    if (s.kind == 0) make_coords_host(s, coords.data());
+    auto copy_rows = [&](char* to_e, char* to_a, const char* from_e, const char* from_a, int64_t k) {
+      std::memcpy(to_e, from_e, (size_t)rb);
+      if (ord::stored(a, k)) std::memcpy(to_a, from_a, (size_t)rb);
+    };
+    switch (phase) {
+      case ordsh::PLAN:
+        ord_plan_host<GORD_RB>(a, false);
+        return 0;
+      case ordsh::LEVEL: {
+        std::vector<int64_t> li;
+        for (int64_t k = a.o_lo; k < a.o_hi; ++k)
+          if (a.o_src[4 * k + 3] == L) li.push_back(k);
+        host_parallel((int64_t)li.size(), g_host_ctx(s, coords.data(), [&](const GCtx& x, int64_t q) {
+                        GOrd::turn(x, a, li[(size_t)q], gen);
+                      }));
+        return 0;
+      }
+      case ordsh::PACK: {
+        int64_t pos = 0;
+        for (int64_t k = a.o_lo; k < a.o_hi; ++k) {
+          if (a.o_src[4 * k + 3] != L) continue;
+          if (pos >= a.x_blk) {
+            a.o_ctl[ord::ERRW] |= ord::ERR_PACK;
+            break;
+          }
+          char* r = reinterpret_cast<char*>(a.sendbuf) + pos * recb;
+          *reinterpret_cast<int64_t*>(r) = k;
+          copy_rows(r + ordsh::HDR, r + ordsh::HDR + rb, GItem::rowp(s, a.W, k), GItem::rowp(s, a.W3, k), k);
+          ++pos;
+        }
+        a.x_ctl[0] = (int32_t)pos;
+        return 0;
+      }
+      case ordsh::UNPACK: {
+        host_parallel(nrec, [&](int64_t i) {
+          const char* r = reinterpret_cast<const char*>(a.recvbuf) + i * recb;
+          const int64_t k = *reinterpret_cast<const int64_t*>(r);
+          if (k < 0 || k >= a.n || (k >= a.o_lo && k < a.o_hi)) return;
+          copy_rows(GItem::rowp(s, a.W, k), GItem::rowp(s, a.W3, k), r + ordsh::HDR, r + ordsh::HDR + rb, k);
+        });
+        a.x_ctl[0] = 0;
+        return 0;
+      }
+      case ordsh::CLOSE: {
+        for (int64_t r = a.o_lo; r < a.o_hi; ++r)
+          if (a.o_src[4 * r + 3] < 0) a.o_ctl[ord::ERRW] |= ord::ERR_NOT_RUN;
+        host_parallel(own, g_host_ctx(s, coords.data(), [&](const GCtx& x, int64_t i) {
+                        const int64_t r = a.o_lo + i;
+                        GOrd::close_row(x, a, r, x.v(s.o_w));
+                        if (a.rowflags) a.rowflags[r] = a.respawn[r] != 0;
+                      }));
+        return 0;
+      }
+      default: {  // LINK
+        for (int64_t r = 0; r < a.n; ++r) a.heads[r] = SRNN_NIL;
+        for (int64_t r = 0; r < a.n; ++r) {
+          int64_t at, te;
+          Dec::decision(a, r, gen + 1, at, te);
+          if (at >= 0) {
+            a.nexts_next[r] = a.heads_next[at];
+            a.heads_next[at] = (uint32_t)r;
+          }
+        }
+        return 0;
+      }
+    }
+  }
+  hipStream_t st = (hipStream_t)a.stream;
+  const unsigned nb = (unsigned)((a.n + TB - 1) / TB), nbo = (unsigned)std::max<int64_t>((own + TB - 1) / TB, 1);
+  if ((phase == ordsh::LEVEL || phase == ordsh::CLOSE) && (!a.scratch || a.scratch_bytes < gsh_scratch_bytes(s, own))) {
+    set_error("runtime-shape sharded ordered generation: scratch missing or shorter than this rank's level and close "
+              "launches need (srnn_generic_ordsh_scratch_bytes)");
+    return -5;
+  }
+  switch (phase) {
+    case ordsh::PLAN:
+      hipLaunchKernelGGL((k_ord_plan<GORD_RB>), dim3(nb), dim3(TB), 0, st, c, a);
+      hipLaunchKernelGGL((k_ord_mark<GORD_RB>), dim3(nb), dim3(TB), 0, st, c, a);
+      hipLaunchKernelGGL((k_ord_count<GORD_RB>), dim3(nb), dim3(TB), 0, st, c, a);
+      hipLaunchKernelGGL((k_ordsh_levels<ShapeFree, StF32>), dim3(nb), dim3(TB), 0, st, a);
+      break;
+    case ordsh::LEVEL: {
+      if (own <= 0) break;
+      // the turns of this level on this rank: at most x_blk (0: not given -- every own turn)
+      const int64_t turns = a.x_blk > 0 ? std::min<int64_t>(a.x_blk, own) : own;
+      WWave g;
+      const bool group = gord_wave_serves(s, g);
+      const bool wave = !group && gord_rnn_serves(s) &&
+                        GORD_HDR + gsh_list_bytes(own) + gsh_rnn_waves(own) * rw_soup_scratch_bytes(s) <= a.scratch_bytes;
+      if (group || wave) {
+        if (hipMemsetAsync(a.scratch, 0, 4, st) != hipSuccess) break;
+        hipLaunchKernelGGL(k_gordsh_list, dim3(nbo), dim3(TB), 0, st, a, L);
+        if (group) gordsh_ww_launch(s, g, a, turns, st);
+        else gordsh_rnn_launch(s, a, std::min<int64_t>(turns, gsh_rnn_waves(own)), st);
+      } else {
+        hipLaunchKernelGGL(k_gordsh_level, dim3(nbo), dim3(TB), 0, st, s, a, L);
+      }
+      break;
+    }
+    case ordsh::PACK:
+      hipLaunchKernelGGL(k_gordsh_pack, dim3(nbo), dim3(TB), 0, st, s, a, L);
+      break;
+    case ordsh::UNPACK:
+      hipLaunchKernelGGL(k_gordsh_unpack, dim3((unsigned)std::max<int64_t>((nrec + TB - 1) / TB, 1)), dim3(TB), 0, st, s,
+                         a, nrec);
+      break;
+    case ordsh::CLOSE:
+      hipLaunchKernelGGL(k_gordsh_close, dim3(nbo), dim3(TB), 0, st, s, a);
+      break;
+    default:
+      hipLaunchKernelGGL((k_ordsh_link<ShapeFree, StF32>), dim3(nb), dim3(TB), 0, st, a);
+      break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error(hipGetErrorString(e));
+    return -3;
+  }
+  return 0;
 }
 
 // lanes of a device launch and the scratch bytes they need
@@ -3045,6 +3404,13 @@ extern "C" int srnn_dispatch_generic(int op, const SrnnCfg* c, const SrnnArgs* a
     }
     return op == OP_ORD_PLAN ? srnn::ord_plan_op<srnn::GORD_RB, void>(*c, *a, true) : srnn::g_soup_ordered(*c, s, *a);
   }
+  if (op == OP_SOUP_ORDERED_SH) {  // ... sharded over ranks, one phase per call
+    if (!srnn::gordsh_serves(s, a->dev != 0, &why)) {
+      srnn::set_error(why);
+      return -5;
+    }
+    return srnn::g_soup_ordered_sh(*c, s, *a);
+  }
   if (op == OP_GEN_FINISH) {  // shape independent: the batched / serial finish of srnn_kernels.h
     SrnnCfg dummy{};
     return srnn::gen_finish<srnn::Weightwise<1, 1>, srnn::StF32>(dummy, *a);
@@ -3113,9 +3479,29 @@ extern "C" int srnn_generic_train_form(const SrnnCfg* c, int dev) {
 // 1 when the runtime-shape engine serves `op` of this configuration on the host (dev 0) / device
 // (dev 1): srnn_generic_op_supported, and the reference-order generation with the shape in hand
 extern "C" int srnn_generic_supports(const SrnnCfg* c, int op, int dev) {
-  if (op != OP_SOUP_ORDERED && op != OP_ORD_PLAN) return srnn_generic_op_supported(op, dev);
+  if (op != OP_SOUP_ORDERED && op != OP_ORD_PLAN && op != OP_SOUP_ORDERED_SH) return srnn_generic_op_supported(op, dev);
   srnn::GShape s;
   const char* why = "";
   if (!srnn::make_gshape(*c, s, &why)) return 0;
+  if (op == OP_SOUP_ORDERED_SH) return srnn::gordsh_serves(s, dev != 0, &why) ? 1 : 0;
   return srnn::gord_serves(s, op, dev != 0, &why) ? 1 : 0;
+}
+
+// the sharded reference-order generation of a runtime shape (OP_SOUP_ORDERED_SH): the device scratch
+// bytes a rank with `own` turns needs -- the level list and the lanes of the level / close launches or,
+// where larger, the recurrent wave slices (-1: not a valid shape) -- and the form of its level launches
+// on the host (dev 0) / device (dev 1) with the knob in force: 0 none, 1 a lane per turn, 2 a group of
+// lanes per turn (k_gordsh_level_ww) or a wave per turn (k_gordsh_level_rnn)
+extern "C" int64_t srnn_generic_ordsh_scratch_bytes(const SrnnCfg* c, int64_t own) {
+  srnn::GShape s;
+  const char* why = "";
+  if (!srnn::make_gshape(*c, s, &why)) return -1;
+  return srnn::gsh_scratch_bytes(s, own < 0 ? 0 : own);
+}
+extern "C" int srnn_generic_ordsh_form(const SrnnCfg* c, int dev) {
+  srnn::GShape s;
+  const char* why = "";
+  if (!srnn::make_gshape(*c, s, &why) || !srnn::gordsh_serves(s, dev != 0, &why)) return 0;
+  srnn::WWave g;
+  return dev && (srnn::gord_wave_serves(s, g) || srnn::gord_rnn_serves(s)) ? 2 : 1;
 }

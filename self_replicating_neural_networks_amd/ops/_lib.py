@@ -204,6 +204,10 @@ def lib():
         L.srnn_generic_ord_scratch_bytes.restype = ctypes.c_int64
         L.srnn_ord_run_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int]
         L.srnn_ord_run_form.restype = ctypes.c_int
+        L.srnn_ordsh_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int]
+        L.srnn_ordsh_form.restype = ctypes.c_int
+        L.srnn_generic_ordsh_scratch_bytes.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int64]
+        L.srnn_generic_ordsh_scratch_bytes.restype = ctypes.c_int64
         L.srnn_train_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int]
         L.srnn_train_form.restype = ctypes.c_int
         L.srnn_mixed_form.argtypes = [ctypes.POINTER(SrnnCfg), ctypes.c_int, ctypes.c_int]
@@ -362,6 +366,23 @@ def ord_run_form(spec, dev: bool = True, dtype_code: int = DTYPE_FP32):
     csrc/srnn_generic.hip k_gord_run_ww) or a whole wave per turn (the Recurrent nets of width >= 8,
     k_gord_run_rnn; both under the knob ``ord_wave``), ``None`` -- no such generation."""
     r = int(lib().srnn_ord_run_form(ctypes.byref(make_cfg(spec, dtype_code)), 1 if dev else 0))
+    return {1: "lane", 2: "wave"}.get(r)
+
+
+def generic_ordsh_scratch_bytes(spec, own: int, dtype: int = DTYPE_FP32) -> int:
+    """Device scratch one rank of a sharded reference-order generation (OP_SOUP_ORDERED_SH) of a runtime
+    shape needs for its ``own`` turns: the level list and the lanes of the level and close launches or,
+    where larger, the recurrent wave slices (csrc/srnn_generic.hip gsh_scratch_bytes)."""
+    return int(lib().srnn_generic_ordsh_scratch_bytes(ctypes.byref(make_cfg(spec, dtype)), int(own)))
+
+
+def ordsh_form(spec, dev: bool = True, dtype_code: int = DTYPE_FP32):
+    """The form of the level launches of a sharded reference-order generation of this architecture on
+    the device (``dev=True``) or the host, with the knobs in force: ``"lane"`` -- a lane per turn,
+    ``"wave"`` -- a group of lanes per turn (the wide Weightwise runtime shapes, k_gordsh_level_ww) or a
+    wave per turn (the Recurrent nets of width >= 8, k_gordsh_level_rnn; both under the knob
+    ``ord_wave``), ``None`` -- no such generation."""
+    r = int(lib().srnn_ordsh_form(ctypes.byref(make_cfg(spec, dtype_code)), 1 if dev else 0))
     return {1: "lane", 2: "wave"}.get(r)
 
 

@@ -161,6 +161,11 @@ def sharded_ordered_bytes(spec: ArchSpec, n_total: int, world: int, dtype=torch.
     b += N * rb                      # _fw: the E version of every row
     b += 2 * 2 * N * 4 + 16          # replicated heads + nexts of both parities, level-pack counters
     b += (1 + world) * cap * recb    # send + receive records of one level
+    dc = K.dtype_code(dtype)
+    if _lib.is_generic(spec, _lib.OP_SOUP_ORDERED_SH, dc):
+        # a runtime shape: the scratch of this rank's level and close launches (a device buffer), shared
+        # with the engine's other runtime-shape operators
+        b += max(_lib.generic_scratch_bytes(spec, cap, dc), _lib.generic_ordsh_scratch_bytes(spec, cap, dc))
     return int(b)
 
 
@@ -512,8 +517,17 @@ class SoupEngine:
         if N > ORDERED_MAX_ROWS:
             raise ValueError("reference-order generations address < 2^30 slots")
         if sharded and not _lib.supports(self.spec, _lib.OP_SOUP_ORDERED_SH, dev_side, self.dtype_code):
-            raise NotImplementedError(f"no sharded reference-order generation for {self.spec}")
+            raise NotImplementedError(
+                f"no sharded reference-order generation for {self.spec}: it exists for every shape that has a "
+                "single-rank one but the big aggregating nets (aggregating, P > 64: csrc/srnn_bignet.h runs their "
+                "reference order on one rank only)")
         dev = self.device
+        if sharded and dev_side and _lib.is_generic(self.spec, _lib.OP_SOUP_ORDERED_SH, self.dtype_code):
+            # a runtime shape (csrc/srnn_generic.hip g_soup_ordered_sh): the level list and the lanes /
+            # wave slices of this rank's level and close launches -- allocated here, never in a generation
+            nbytes = _lib.generic_ordsh_scratch_bytes(self.spec, self.n, self.dtype_code)
+            if self._scratch is None or self._scratch.numel() < nbytes:
+                self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         C = int(self.execution.order_levels)
         self.order_levels = C
         self._ord_n = N
@@ -687,6 +701,16 @@ class SoupEngine:
             return None
         form = _lib.ord_run_form(self.spec, dev=self.device.type == "cuda", dtype_code=self.dtype_code)
         return "lane" if form == "wave" and self._ord_mode == "kernel" else form
+
+    def ordered_sharded_form(self) -> Optional[str]:
+        """The form of the level launches of this engine's sharded reference-order generations with the
+        library knobs in force now (``_lib.ordsh_form``): ``"lane"`` -- a lane per turn, ``"wave"`` -- a
+        group of lanes per turn (the wide Weightwise runtime shapes) or a wave per turn (the Recurrent
+        nets of width >= 8), both on the device under the knob ``ord_wave``; ``None`` for an engine of
+        another order or a single-rank one (``ordered_run_form``)."""
+        if self.order != "sequential" or not self.dist.enabled:
+            return None
+        return _lib.ordsh_form(self.spec, dev=self.device.type == "cuda", dtype_code=self.dtype_code)
 
     def ordered_error(self) -> int:
         """This rank's reference-order error bits (ORD_ERRORS), sticky over the engine's life (0:
@@ -1129,8 +1153,8 @@ class SoupEngine:
         caps, maxl = self._sh_level_caps(N, R)  # records per rank and level: the same on every rank
         recw = self._sh_recb // 8
         for L in range(maxl + 1):
-            run(_lib.ORDSH_LEVEL, L)
             cap = int(caps[L])
+            run(_lib.ORDSH_LEVEL, L, x_blk=cap)  # (a runtime shape sizes its level list's launch by it)
             if cap == 0:
                 continue
             send = self._sh_send[:cap * recw]
